@@ -1,19 +1,30 @@
 """Benchmark: lstmformer training frames/s (BASELINE.json metric), fp32, synthetic data.
 
     python bench.py [--gpus N --steps K --warmup W]          (N > 1 under torch.distributed.run)
+    python bench.py --full [...]                             (every other figure as well, see below)
+    python bench.py --dump-outputs DIR [...]                 (what the last timed step computed, as .npy)
 
 A step = Metaformer.training_step (fwd + masked Huber loss) + backward +
 RCCL gradient all-reduce (N > 1) + fused AdamW, on B=64 x T=300 frames per
-GPU (weak scaling).  Inputs are resident in HBM before timing.  Prints ONE
-JSON line on rank 0 with the live roofline of the dominant kernel (HIP events
-around its launches inside the timed region) and the CPU oracle baseline
-timed on this host (rank 0, N=1 only).
+GPU (weak scaling).  Inputs are resident in HBM before timing and identical
+from run to run (fixed seeds).  A plain run sets up, warms up, times the K
+steps and prints ONE JSON line on rank 0 (metric, value, ms_per_step, the
+whole-step roofline from the step's algorithmic FLOPs): nothing else runs.
 
-At N=1 the same line carries a ``secondary`` block with the other 1-GPU
-BASELINE configs, each graph-replayed with its own ms/step,
-frames/s, whole-step roofline, dominant-kernel roofline and a CPU baseline on a
-bounded sample: C2 simple_lstm (fp32 and bf16), C3 lstm_with_sampling scheduled
-sampling, and lstmformer autoregressive generation (§8f rank 1).
+``--dump-outputs DIR`` writes, after the timed steps, what a caller of the
+timed step holds after its last step: ``loss.npy``, ``params.npy`` (the flat
+parameter buffer after AdamW) and ``grads.npy`` (the flat gradient buffer),
+float32, the two buffers as one fixed seeded sample each (write_outputs).
+
+``--full`` adds what takes runs of its own: the live roofline of the dominant
+kernel (HIP events around its launches in two eager steps after the timed
+region), the CPU oracle baseline timed on this host (rank 0, N=1 only) and,
+at N=1, a ``secondary`` block with the other 1-GPU BASELINE configs (SURVEY
+§8d), each graph-replayed with its own ms/step, frames/s, whole-step
+roofline, dominant-kernel roofline and a CPU baseline on a bounded sample:
+C2 simple_lstm (fp32 and bf16), C3 lstm_with_sampling scheduled sampling,
+and lstmformer autoregressive generation (§8f rank 1).  ``--secondary 0`` /
+``--cpu-baseline 0`` switch those two legs off under ``--full``.
 """
 import argparse
 import json
@@ -114,17 +125,24 @@ def parse(argv=None):
     ap.add_argument("--dry-run", type=int, default=0,
                     help="1 = exercise the launch / rendezvous / barrier / max-over-ranks timing / JSON on the CPU "
                          "(gloo, a flat-buffer all-reduce as the step), no GPU")
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: live per-kernel roofline (eager probe steps), "
+                         "the secondary configs and the CPU baselines (see --secondary, --cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's loss, parameters and gradients as DIR/<name>.npy "
+                         "(float32; rank 0)")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--seq", type=int, default=300)
     ap.add_argument("--ratio", type=int, default=1, help="audio frames per prediction frame (8 = reference rate)")
     ap.add_argument("--graph", type=int, default=1, help="replay the step as a HIP graph")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="with --full: time the CPU baselines")
     ap.add_argument("--cpu-steps", type=int, default=5, help="timed CPU steps of the headline baseline")
     ap.add_argument("--cpu-warmup", type=int, default=2)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every physical core this process may use")
-    ap.add_argument("--secondary", type=int, default=1, help="time the other 1-GPU BASELINE configs (N=1 only)")
+    ap.add_argument("--secondary", type=int, default=1,
+                    help="with --full: time the other 1-GPU BASELINE configs (N=1 only)")
     ap.add_argument("--wgrad-stream", type=int, default=1,
                     help="weight-gradient GEMMs on a side stream (functional._side); 0 = one stream")
     ap.add_argument("--wgrad-defer", type=int, default=1,
@@ -141,9 +159,40 @@ def parse(argv=None):
                     help="N>1: before timing, check that one step's rank-averaged gradient equals a single-rank step "
                          "on the concatenation of every rank's shard (reported as ddp_check)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:      # a plain run does only what the headline figure needs
+        args.secondary = args.cpu_baseline = 0
     if args.shared_device_gloo and args.comm != "torch":
         ap.error("--shared-device-gloo runs the exchange on torch.distributed gloo; --comm native needs RCCL")
     return args
+
+
+DUMP_MAX_BYTES = 60_000_000   # --dump-outputs: every file together (64 MB allowed, headers included)
+DUMP_SEED = 0
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: ``arrays`` (name -> tensor) as ``path/<name>.npy``, float64 tensors as float64
+    and every other dtype as float32, flattened.  The files share DUMP_MAX_BYTES equally; a tensor
+    over its share is written as a fixed sample, the elements at the sorted indices
+    ``numpy.random.RandomState(DUMP_SEED).choice(numel, share, replace=False)``, the same indices in
+    every run and for every tensor of that size.  Returns name -> elements written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    picks, written = {}, {}
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1).cpu()
+        a = t.numpy() if t.dtype == torch.float64 else t.float().numpy()
+        keep = share // a.itemsize
+        if a.size > keep:
+            if (a.size, keep) not in picks:
+                picks[a.size, keep] = np.sort(np.random.RandomState(DUMP_SEED).choice(a.size, keep, replace=False))
+            a = a[picks[a.size, keep]]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = int(a.size)
+    return written
 
 
 def _free_port():
@@ -343,6 +392,8 @@ def dry_run(args):
             dist.destroy_process_group()
         return
     ms = 1000.0 * elapsed / max(1, args.steps)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, {"allreduce_buffer": buf})
     mc, _, _ = C.lstmformer_config(ratio=args.ratio)
     step_flop = (model_flops_per_frame(mc, args.ratio) + attn_flops_per_frame(mc, args.ratio, args.seq)) \
         * args.batch * args.seq
@@ -649,6 +700,7 @@ def headline_dict(args, world, ms, value, step_flop, roof, kernels, seen, allred
         "metric": METRIC, "value": None if value is None else round(value, 2), "unit": "frames/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp32", "data": "synthetic",
+        "full": bool(args.full),
         "config": {"workload": "lstmformer train step (fwd+Huber+bwd+AdamW), BASELINE configs[3]/[4]",
                    "model": "lstmformer H=256 blocks=5 enc_layers=5 heads=4 bottleneck=64 (13,052,678 params)",
                    "global_batch": args.batch * world, "seq_len": args.seq, "audio_ratio": args.ratio,
@@ -903,10 +955,13 @@ def main():
 
     one = torch.ones((), device=dev)   # d loss / d loss, made once (backward() would fill a new one per step)
 
+    last = {}    # the loss tensor of the latest step (inside a captured graph: the buffer every replay fills)
+
     def fwd_bwd():
         opt.zero_grad()
         loss = model.training_step(list(batch))["loss"]
         loss.backward(one)
+        last["loss"] = loss.detach()
         return loss
 
     def step():
@@ -962,15 +1017,18 @@ def main():
     ms = 1000.0 * elapsed / args.steps
     frames = args.batch * args.seq * world
     value = frames * args.steps / elapsed
+    if args.dump_outputs and rank == 0:   # before anything below steps the model again
+        n = write_outputs(args.dump_outputs, {"loss": last["loss"], "params": opt.flat, "grads": opt.flat_grad})
+        progress(f"wrote {', '.join(f'{k}.npy ({v})' for k, v in n.items())} to {args.dump_outputs}")
 
-    # live per-family kernel timing: HIP events recorded on the launch stream around every library
+    # --full: live per-family kernel timing: HIP events recorded on the launch stream around every library
     # call of two eager steps right after the timed region (a graph replay cannot be bracketed);
     # each launch carries its algorithmic FLOPs (functional._probe), so achieved = FLOPs / time
     # (the replay's stream schedule: weight gradients on the side stream, so a bracketed launch runs
     # beside the same work as in the graph; a weight-gradient bracket includes its split-K reduce)
     # (every rank steps, the all-reduce is collective; rank 0 records)
-    if shared:
-        kernels, roof = {}, None    # a test of the code path: ranks take turns, no kernel figures
+    if shared or not args.full:
+        kernels, roof = {}, None    # shared: a test of the code path, ranks take turns, no kernel figures
     elif rank == 0:
         kernels, roof = _probe_steps(step, 2)
         if roof is not None:
@@ -998,7 +1056,6 @@ def main():
     if rank == 0:
         progress(f"headline {ms:.3f} ms/step")
     if rank == 0 and world == 1 and args.secondary:
-
         out["secondary"] = secondary_summary(secondary(args, dev))
     if rank == 0 and world == 1 and args.cpu_baseline:
         progress("headline CPU baseline")

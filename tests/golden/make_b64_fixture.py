@@ -42,6 +42,7 @@ from multimodalreactiongeneration_amd import configs as C  # noqa: E402
 from multimodalreactiongeneration_amd.model import Metaformer, LSTMwithSample, SimpleLSTM  # noqa: E402
 from multimodalreactiongeneration_amd.synthetic import make_batch, make_simple_batch  # noqa: E402
 from oracle import mrg_oracle as O  # noqa: E402
+from tests.golden_util import save  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 NSAMPLE = 256
@@ -132,8 +133,7 @@ def main(names):
     for name in names or list(WORKLOADS):
         t0 = time.time()
         out = WORKLOADS[name]()
-        path = os.path.join(HERE, name + ".npz")
-        np.savez_compressed(path, **out)
+        path = " + ".join(save(name, out))   # in parts where one file would pass 1 MiB (tests/golden_util.py)
         loss = f"loss {float(out['loss']):.9f}, " if "loss" in out else ""
         print(f"wrote {path}: {loss}{len(out)} arrays, {time.time() - t0:.0f} s", flush=True)
 

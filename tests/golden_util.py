@@ -8,8 +8,55 @@ import torch
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
+PART_BYTES = 900_000   # no committed file over 1 MiB: a larger fixture is name.npz, name.1.npz, ...
+
+
+class _Parts:
+    """The arrays of a fixture stored in several .npz files, read as one (``d[key]``, ``d.files``)."""
+
+    def __init__(self, parts):
+        self._where = {k: p for p in parts for k in p.files}
+        self.files = list(self._where)
+
+    def __getitem__(self, key):
+        return self._where[key][key]
+
+    def __contains__(self, key):
+        return key in self._where
+
+
+def _part_path(name, i):
+    return os.path.join(GOLDEN, name + (f".{i}.npz" if i else ".npz"))
+
+
 def load(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    parts = [np.load(_part_path(name, 0), allow_pickle=False)]
+    while os.path.exists(_part_path(name, len(parts))):
+        parts.append(np.load(_part_path(name, len(parts)), allow_pickle=False))
+    return parts[0] if len(parts) == 1 else _Parts(parts)
+
+
+def save(name, arrays):
+    """Write a fixture (the generators' np.savez_compressed), in key order, starting a new part
+    whenever the arrays, their .npy headers and zip entries would pass PART_BYTES.  Returns the paths."""
+    groups, size = [{}], 0
+    for k, v in arrays.items():
+        n = np.asarray(v).nbytes + 2 * len(k) + 256
+        if groups[-1] and size + n > PART_BYTES:
+            groups.append({})
+            size = 0
+        groups[-1][k] = v
+        size += n
+    paths = []
+    for i, g in enumerate(groups):
+        np.savez_compressed(_part_path(name, i), **g)
+        assert os.path.getsize(_part_path(name, i)) < (1 << 20), _part_path(name, i)
+        paths.append(_part_path(name, i))
+    i = len(groups)
+    while os.path.exists(_part_path(name, i)):   # a regenerated fixture that needs fewer parts than before
+        os.remove(_part_path(name, i))
+        i += 1
+    return paths
 
 
 def config(d):

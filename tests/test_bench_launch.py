@@ -67,6 +67,60 @@ def test_headline_is_the_last_line_and_small():
         assert s["secondary"] in out["secondary"] and "cpu_baseline" in s and "whole_step_roofline" in s
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("mrg_bench_under_test", BENCH)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_plain_run_is_lean_and_full_restores_every_leg():
+    """Without --full the secondary configs and the CPU baselines are off whatever their own switches
+    say (the probe steps key on args.full itself); --full runs them as before, each leg still
+    switchable; --steps is the number of timed steps and must be at least 1."""
+    import pytest
+    b = _bench_module()
+    a = b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.secondary, a.cpu_baseline, a.steps, a.warmup, a.dump_outputs) == (False, 0, 0, 7, 2, None)
+    a = b.parse(["--secondary", "1", "--cpu-baseline", "1"])
+    assert (a.full, a.secondary, a.cpu_baseline) == (False, 0, 0)
+    a = b.parse(["--full"])
+    assert (a.full, a.secondary, a.cpu_baseline) == (True, 1, 1)
+    a = b.parse(["--full", "--secondary", "0", "--dump-outputs", "d"])
+    assert (a.full, a.secondary, a.cpu_baseline, a.dump_outputs) == (True, 0, 1, "d")
+    with pytest.raises(SystemExit):
+        b.parse(["--steps", "0"])
+
+
+def test_write_outputs_dtypes_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 files (float64 stays float64), every file together inside the budget, a
+    tensor over its share written as the same seeded sample in every run and for every tensor of that
+    size, smaller tensors whole."""
+    import numpy as np
+    import torch
+    b = _bench_module()
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 1600)          # four files: 400 bytes of data each
+    big = torch.arange(1000, dtype=torch.float32).reshape(10, 100)
+    arrays = {"loss": torch.tensor(0.25), "params": big, "grads": -big.to(torch.bfloat16),
+              "wide": torch.arange(1000, dtype=torch.float64)}
+    for run in ("a", "b"):
+        n = b.write_outputs(str(tmp_path / run), arrays)
+        assert n == {"loss": 1, "params": 100, "grads": 100, "wide": 50}
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in arrays}
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["grads.npy", "loss.npy", "params.npy", "wide.npy"]
+    assert {k: str(v.dtype) for k, v in got.items()} == {"loss": "float32", "params": "float32", "grads": "float32",
+                                                         "wide": "float64"}
+    assert sum(v.nbytes for v in got.values()) <= 1600
+    idx = np.sort(np.random.RandomState(b.DUMP_SEED).choice(1000, 100, replace=False))
+    assert got["loss"].tolist() == [0.25]
+    assert np.array_equal(got["params"], idx.astype(np.float32))
+    assert np.array_equal(got["grads"], -big.to(torch.bfloat16).float().reshape(-1).numpy()[idx])
+    assert len(np.unique(got["wide"])) == 50 and np.all(np.diff(got["wide"]) > 0)
+    for k in arrays:
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / (k + ".npy")))
+
+
 def test_more_gpus_than_visible_fails_loudly():
     env = _env(HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
     r = _run(["--gpus", "2", "--steps", "1"], env, timeout=120)

@@ -23,7 +23,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.
 tail -1 $O/smoke.log
 cd /tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- \
-  python3 $R/bench.py --steps 5 --warmup 2 --cpu-baseline 0 --secondary 0 > $O/trace.log 2>&1 \
+  python3 $R/bench.py --full --steps 5 --warmup 2 --cpu-baseline 0 --secondary 0 > $O/trace.log 2>&1 \
   || { echo "trace failed"; tail -20 $O/trace.log; exit 1; }
 cd $R
 T=$(ls $O/trace/*/run_kernel_trace.csv $O/trace/run_kernel_trace.csv 2>/dev/null | head -1)
@@ -33,7 +33,7 @@ python3 tools/tools_timeline.py $T 2 > $O/timeline.txt
 S=$(ls $O/trace/*/run_kernel_stats.csv $O/trace/run_kernel_stats.csv 2>/dev/null | head -1)
 python3 tools/tools_prof_summary.py $S > $O/kernel_summary.txt 2>/dev/null || cp $S $O/kernel_stats.csv
 echo "trace ok"
-timeout -k 10 600 python bench.py > $O/bench.json.log 2>&1 || { tail -20 $O/bench.json.log; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench.json.log 2>&1 || { tail -20 $O/bench.json.log; exit 1; }
 grep -o '"ms_per_step": [0-9.]*' $O/bench.json.log | tail -1
 exit 0
 fi
@@ -57,16 +57,16 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.
 tail -1 $O/smoke.log
 exit 0
 fi
-timeout -k 10 600 python bench.py > $O/bench.json.log 2>&1 || { tail -20 $O/bench.json.log; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench.json.log 2>&1 || { tail -20 $O/bench.json.log; exit 1; }
 grep -o '"ms_per_step": [0-9.]*' $O/bench.json.log | head -1
 cd /tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- \
-  python3 $R/bench.py --steps 5 --warmup 2 --cpu-baseline 0 --secondary 0 > $O/trace.log 2>&1 \
+  python3 $R/bench.py --full --steps 5 --warmup 2 --cpu-baseline 0 --secondary 0 > $O/trace.log 2>&1 \
   || { echo "trace failed"; tail -20 $O/trace.log; exit 1; }
 echo "trace ok"
 for c in $([ "${PMC:-1}" = "1" ] && echo FETCH_SIZE WRITE_SIZE); do
   timeout -k 10 400 rocprofv3 --pmc $c -d $O/pmc/$c -o pmc --output-format csv -- \
-    python3 $R/bench.py --graph 0 --wgrad-stream 0 --cpu-baseline 0 --secondary 0 --steps 1 --warmup 1 \
+    python3 $R/bench.py --full --graph 0 --wgrad-stream 0 --cpu-baseline 0 --secondary 0 --steps 1 --warmup 1 \
     > $O/pmc_$c.log 2>&1 || { echo "pmc $c failed"; tail -20 $O/pmc_$c.log; exit 1; }
   echo "pmc $c ok"
 done
