@@ -216,7 +216,10 @@ int mrg_gru_bwd(int B, int T, int H, const float* w_hh, const float* gates, long
  * The per-frame kernels of lstm_with_sampling's autoregressive training step
  * (LSTMwithSample.head_motion_generation / generate_one_step, lstm_with_sample.py:379-433), whose
  * layered LSTM restarts from zero state every frame.  Host side: decode.py.  All
- * per-frame tensors are [B, ...] row-major slabs; H <= 256 and H % 4 == 0, HB <= 64, FO <= 8.
+ * per-frame tensors are [B, ...] row-major slabs; H <= 256 and H % 4 == 0, HB <= 64, FO <= 8 (the
+ * persistent loops below take FO <= 16; their FO = 9..16 is pinned against float64 by
+ * tests/test_gpu_models.py test_ssd_persistent_loop_wide_outputs_vs_f64, and decode.py refuses a
+ * gradient through FO > 8 when the backward loop cannot run, e.g. with one layer).
  * mrg_ssd_gate_cell_fwd: one zero-state LSTM layer of one frame for B rows; its input X [B, H]
  *   is mode 0: xin, mode 1: LayerNorm(hp + rp) of the previous layer (gamma, beta; its mean /
  *   rstd written).  X goes to xout (unless it is xin); gates [B, 4H] (i, f, g, o), c, h [B, H].

@@ -42,6 +42,12 @@ _LOOP = [os.environ.get("MRG_SSD_LOOP", "1") == "1"]
 _LOOP_BWD = [os.environ.get("MRG_SSD_LOOP_BWD", "1") == "1"]
 
 
+def _bwd_loop(lib, B, H, HB, FO, nl):
+    """Whether the backward runs as the persistent loop (else: the per-frame kernels, FO <= 8)."""
+    return bool(nl >= 2 and _LOOP_BWD[0] and H == 256 and HB == 64 and FO <= 16 and nl <= 4
+                and lib.mrg_ssd_loop_bwd_fits(B, 0) == 1)
+
+
 class _SSDecodeFn(Function):
     """y [B, T, FO] of the scheduled-sampling decode; see the module docstring.
 
@@ -67,6 +73,13 @@ class _SSDecodeFn(Function):
         HB, FO = w1.shape[0], w2.shape[0]
         if FO != FM:
             raise RuntimeError("the prediction feeds back as motion_self: output size must equal its features")
+        if FO > 8 and any(ctx.needs_input_grad) and not _bwd_loop(lib, B, H, HB, FO, nl):
+            # the forward loop takes FO <= 16 but only the backward loop (nl >= 2) does too: refuse here,
+            # not in the middle of a backward pass whose first launches are already issued
+            raise RuntimeError(
+                f"scheduled_sampling_decode: a gradient through FO={FO} > 8 output features needs the persistent "
+                f"backward loop (mrg_ssd_loop_bwd: H=256, HB=64, FO<=16, 2<=nl<=4, grid resident; got H={H} HB={HB} "
+                f"nl={nl}); the per-frame backward (mrg_ssd_ffn_bwd) takes FO <= 8")
         # X_f [T, B, F] = [sampler | partner | ms_in], time-major so a frame is one slab; the ms_in
         # columns are written by the layer-1 kernel of each frame (the sampling select)
         xf = torch.empty(T, B, F, device=dev, dtype=F32)
@@ -176,8 +189,7 @@ class _SSDecodeFn(Function):
         dX = [torch.empty(T, B, H, device=dev, dtype=F32) for _ in range(nl)]  # dX[0] = dfeat
         slab, gslab, zslab = B * H, B * 4 * H, B * HB
         ext = nl >= 2
-        loop = (ext and _LOOP_BWD[0] and H == 256 and HB == 64 and FO <= 16 and nl <= 4
-                and lib.mrg_ssd_loop_bwd_fits(B, 0) == 1)
+        loop = _bwd_loop(lib, B, H, HB, FO, nl)
         # W_ih^T copies: the per-frame dX = dG W_ih reads both operands k-contiguous (float4)
         w_t = [None if (loop or (ext and i == 0)) else lay[0].t().contiguous() for i, lay in enumerate(layers)]
         # v = [W1 gamma | W1 beta] [HB, 2] of the last LayerNorm: its row sums through W1 (decode.hip)

@@ -34,6 +34,19 @@ SD = Dict[str, Tensor]
 # summation order; with the GPU's side injected the float64 answer is the GPU's own function of
 # its inputs, so the comparison holds 1e-4 everywhere (tests/test_gpu_models.py).
 RELU_MASKS: Optional[Dict[str, Tensor]] = None
+# Statistics of the injected masks against this restatement's own signs (tests only; None = off, the
+# default: relu() then does exactly what it does without it).  With RELU_MASKS and RELU_STATS both set,
+# relu() records per masked layer {n: pre-activations, flips: count of mask != (x > 0), max_flip: the
+# largest |x| over flipped positions (0 without one), rms: sqrt(mean(x^2)), near: count of
+# |x| <= RELU_BAND * rms}.  No second, unmasked run is needed to judge a flip: x here is the float64
+# pre-activation computed from upstream layers evaluated at the injected masks, and the EARLIEST layer
+# in dataflow order with an illegitimate flip (one at an |x| far from 0) sees an upstream that differs
+# from the unmasked restatement only by legitimate, rounding-size flips, so its x is the restatement's
+# own pre-activation to well inside the band.  A forward that puts ReLUs on the wrong side therefore
+# shows at least its first such layer here with max_flip > RELU_BAND * rms (tests/golden_util.py
+# relu_flips_ok, tests/test_gpu_models.py _check_vs_f64).
+RELU_STATS: Optional[Dict[str, Dict[str, float]]] = None
+RELU_BAND = 1e-5
 
 
 # --------------------------------------------------------------------------- ops
@@ -49,6 +62,17 @@ def relu(x: Tensor, prefix: str) -> Tensor:
         return torch.relu(x)
     if m.shape != x.shape:
         raise ValueError(f"oracle.relu: mask {tuple(m.shape)} for {prefix} but pre-activation {tuple(x.shape)}")
+    if RELU_STATS is not None:
+        xd = x.detach()
+        flipped = m.to(torch.bool) != (xd > 0)
+        rms = math.sqrt(float(xd.double().pow(2).mean())) if xd.numel() else 0.0
+        RELU_STATS[prefix] = {
+            "n": xd.numel(),
+            "flips": int(flipped.sum()),
+            "max_flip": float(xd[flipped].abs().max()) if bool(flipped.any()) else 0.0,
+            "rms": rms,
+            "near": int((xd.abs() <= RELU_BAND * rms).sum()),
+        }
     return x * m.to(x.dtype)
 
 

@@ -75,6 +75,30 @@ def prefixed(d, prefix, device="cpu"):
     return {k[len(prefix):]: torch.from_numpy(d[k]).to(device) for k in d.files if k.startswith(prefix)}
 
 
+def relu_flip_totals(stats):
+    """(total flips, the largest flipped |z| / rms over the layers and its layer (None without a flip),
+    total near) of an oracle.RELU_STATS record."""
+    worst, where = 0.0, None
+    for k, s in stats.items():
+        r = s["max_flip"] / s["rms"] if s["max_flip"] > 0 else 0.0
+        if s["flips"] and (where is None or r > worst):
+            worst, where = r, k
+    return sum(s["flips"] for s in stats.values()), worst, where, sum(s["near"] for s in stats.values())
+
+
+def relu_flips_ok(stats, band, max_flips=32):
+    """The bound on injected ReLU masks (oracle.RELU_MASKS / RELU_STATS): the masks may differ from the
+    float64 oracle's own signs only where the oracle's pre-activation is within rounding of the kink,
+    |z| <= band * rms(z) of its layer, and at no more than max_flips positions in all.  False for an
+    empty record: a check that saw no masked layer has checked nothing."""
+    if not stats:
+        return False
+    for s in stats.values():
+        if s["max_flip"] > band * s["rms"]:
+            return False
+    return sum(s["flips"] for s in stats.values()) <= max_flips
+
+
 def rel_err(a, b):
     a = torch.as_tensor(a).double().cpu()
     b = torch.as_tensor(b).double().cpu()

@@ -1542,3 +1542,211 @@ def test_attention_single_pass_backward_matches_two_pass(B, Tq, Tk, causal, ragg
         oo.backward(do[b].double().view(Tq, Hh, D).transpose(0, 1))
         ref = qq.grad.transpose(0, 1).reshape(Tq, E)
         assert rel_err(dq1[b], ref) < 1e-4
+
+
+# ---------------------------------------------------------------- helper kernels of the C ABI, one by one
+# (inside the models they run at E = 256 and square weights only)
+_TP_SHAPES = [(1, 1), (1, 70), (70, 1), (32, 32), (33, 31), (64, 96), (0, 5)]
+_PAD = 64   # spare floats (bf16 triples) before and after every destination
+
+
+def _tp_mix():
+    """33 matrices (two launches of the 32-per-launch chunking, the second holding one 33 x 31 matrix) of
+    mixed shapes: single rows / columns, one full tile, ragged tiles, several tiles, an empty matrix."""
+    g = torch.Generator().manual_seed(33)
+    shapes = [_TP_SHAPES[i % len(_TP_SHAPES)] for i in range(33)]
+    assert shapes[32] == (33, 31)
+    return shapes, [torch.randn(r, c, generator=g).to(DEV) for r, c in shapes]
+
+
+def test_transpose_batched_mixed_shapes_two_launches():
+    """mrg_transpose_batched: dst_i = src_i^T bitwise for the 33-matrix mix, and nothing outside
+    [cols_i][rows_i] written (sentinel floats before and after every destination)."""
+    import ctypes
+    from multimodalreactiongeneration_amd import _lib as L
+    from multimodalreactiongeneration_amd import functional as Fn
+    lib = L.load()
+    shapes, srcs = _tp_mix()
+    n = len(srcs)
+    SENT = -12345.0
+    bufs = [torch.full((2 * _PAD + r * c,), SENT, device=DEV) for r, c in shapes]
+    VP, CI = ctypes.c_void_p, ctypes.c_int
+    L.check(lib.mrg_transpose_batched(
+        n, (VP * n)(*[s.data_ptr() for s in srcs]), (VP * n)(*[b.data_ptr() + 4 * _PAD for b in bufs]),
+        (CI * n)(*[r for r, _ in shapes]), (CI * n)(*[c for _, c in shapes]), Fn._stream()), "transpose")
+    torch.cuda.synchronize()
+    for i, ((r, c), s, b) in enumerate(zip(shapes, srcs, bufs)):
+        body = b[_PAD:_PAD + r * c].view(c, r)
+        assert torch.equal(body.view(torch.int32), s.t().contiguous().view(torch.int32)), (i, r, c)
+        assert bool((b[:_PAD] == SENT).all()) and bool((b[_PAD + r * c:] == SENT).all()), (i, r, c)
+
+
+def test_split_planes_batched_mixed_shapes_two_launches():
+    """mrg_split_planes_batched on the same mix, every other matrix transposed: the three bf16 planes laid
+    out [3][R'][C'] sum (in float64) to the source within 2^-24 |v| elementwise (include/mrg.h), each plane
+    holds what it should (the first is the bf16 rounding of v), nothing outside them written."""
+    import ctypes
+    from multimodalreactiongeneration_amd import _lib as L
+    from multimodalreactiongeneration_amd import functional as Fn
+    lib = L.load()
+    shapes, srcs = _tp_mix()
+    n = len(srcs)
+    SENT = 0x5A5B
+    trs = [i % 2 for i in range(n)]
+    bufs = [torch.full((2 * _PAD + 3 * r * c,), SENT, dtype=torch.int16, device=DEV) for r, c in shapes]
+    VP, CI = ctypes.c_void_p, ctypes.c_int
+    L.check(lib.mrg_split_planes_batched(
+        n, (VP * n)(*[s.data_ptr() for s in srcs]), (VP * n)(*[b.data_ptr() + 2 * _PAD for b in bufs]),
+        (CI * n)(*[r for r, _ in shapes]), (CI * n)(*[c for _, c in shapes]), (CI * n)(*trs), Fn._stream()), "split")
+    torch.cuda.synchronize()
+    for i, ((r, c), s, b, tr) in enumerate(zip(shapes, srcs, bufs, trs)):
+        assert bool((b[:_PAD] == SENT).all()) and bool((b[_PAD + 3 * r * c:] == SENT).all()), (i, r, c)
+        want = (s.t() if tr else s).contiguous().cpu()
+        bits = b[_PAD:_PAD + 3 * r * c].cpu().view(3, *want.shape).to(torch.int32)
+        planes = ((bits & 0xFFFF) << 16).view(torch.float32)
+        assert torch.equal(planes[0], want.to(torch.bfloat16).to(torch.float32)), (i, r, c, tr)
+        resid = (planes.double().sum(0) - want.double()).abs()
+        assert bool((resid <= 2.0 ** -24 * want.double().abs()).all()), (i, r, c, tr, resid.max().item())
+
+
+@pytest.mark.parametrize("two", [False, True], ids=["out", "out+out2"])
+@pytest.mark.parametrize("beta", [0.0, 1.0])
+@pytest.mark.parametrize("B,T,N", [(1, 2, 1), (1, 38, 45), (64, 300, 6), (12, 26, 1024)])
+def test_colsum_rowmap_beta_and_mirror(B, T, N, beta, two):
+    """mrg_colsum_f32 over rows (1, 37, 19136, 300) x N through a RowMap, the time-shifted [B, T-1, N] view
+    x[:, 1:] of a [B, T, N] tensor (rdiv = T - 1, ld_hi = T N), vs the float64 column sums: within
+    1e-6 of the column's sum of magnitudes (with beta = 1 the prior is one more term of that sum); with
+    beta = 0 a NaN prior does not survive; out2, when given, receives bitwise the same."""
+    from multimodalreactiongeneration_amd import functional as Fn
+    g = torch.Generator().manual_seed(B * T + N)
+    x = torch.randn(B, T, N, generator=g).to(DEV)
+    rows = B * (T - 1)
+    prior = torch.randn(N, generator=g)
+    out = (prior if beta else torch.full((N,), float("nan"))).to(DEV).clone()
+    out2 = out.clone() if two else None
+    guard = torch.full((N + 2 * _PAD,), -7.0, device=DEV)   # out at an offset, sentinels around it
+    guard[_PAD:_PAD + N] = out
+    Fn.colsum(rows, N, Fn._ptr(x, N), N, Fn._ptr(guard, _PAD), out2=Fn._ptr(out2), beta=beta, ld_hi=T * N,
+              rdiv=T - 1, device=x.device)
+    torch.cuda.synchronize()
+    xs = x[:, 1:].double().cpu().reshape(rows, N)
+    exact = xs.sum(0) + beta * prior.double()
+    bound = 1e-6 * (xs.abs().sum(0) + beta * prior.double().abs())
+    got = guard[_PAD:_PAD + N].cpu()
+    assert bool(torch.isfinite(got).all())
+    assert bool(((got.double() - exact).abs() <= bound).all()), ((got.double() - exact).abs() / bound).max().item()
+    assert bool((guard[:_PAD] == -7.0).all()) and bool((guard[_PAD + N:] == -7.0).all())
+    if two:
+        assert torch.equal(out2.cpu().view(torch.int32), got.view(torch.int32))
+
+
+@pytest.mark.parametrize("beta", [0.0, 1.0])
+@pytest.mark.parametrize("n0,n1,E", [(3, 5, 4), (64, 300, 256), (1, 7, 36)])
+def test_swap01_bitwise(n0, n1, E, beta):
+    """mrg_swap01: dst [n1][n0][E] = src [n0][n1][E] bitwise (beta = 0, over a NaN prior) and
+    dst + src^T in one fp32 add (beta = 1), nothing past dst written."""
+    from multimodalreactiongeneration_amd import _lib as L
+    from multimodalreactiongeneration_amd import functional as Fn
+    lib = L.load()
+    g = torch.Generator().manual_seed(n0 + n1 + E)
+    src = torch.randn(n0, n1, E, generator=g).to(DEV)
+    prior = torch.randn(n1, n0, E, generator=g).to(DEV) if beta else torch.full((n1, n0, E), float("nan"), device=DEV)
+    buf = torch.full((n0 * n1 * E + _PAD,), -7.0, device=DEV)
+    buf[:n0 * n1 * E] = prior.reshape(-1)
+    L.check(lib.mrg_swap01(n0, n1, E, Fn._ptr(src), Fn._ptr(buf), beta, Fn._stream()), "swap01")
+    torch.cuda.synchronize()
+    want = src.transpose(0, 1).contiguous()
+    if beta:
+        want = prior + want
+    assert torch.equal(buf[:n0 * n1 * E].view(torch.int32), want.reshape(-1).view(torch.int32))
+    assert bool((buf[n0 * n1 * E:] == -7.0).all())
+
+
+def test_zero_padding_ragged_tail_and_offsets():
+    """mrg_zero_padding: y = x * (x != -100) exactly for n not a multiple of 4 (the scalar tail after the
+    float4 body, more than one block), at buffers 16 bytes into their allocations, padding values in the
+    body and in the tail, nothing past n written; a pointer off the 16-byte grid is refused on the host,
+    and functional.zero_padding on such a view still returns the exact result."""
+    from multimodalreactiongeneration_amd import _lib as L
+    from multimodalreactiongeneration_amd import functional as Fn
+    lib = L.load()
+    g = torch.Generator().manual_seed(5)
+    for n in (1, 2, 3, 7, 1021, 1026, 4099):
+        x = torch.randn(n + 4, generator=g)
+        x[torch.rand(n + 4, generator=g) < 0.3] = -100.0
+        x[n + 3] = -100.0   # the last element of the range
+        x = x.to(DEV)
+        y = torch.full((n + 4 + _PAD,), -7.0, device=DEV)
+        L.check(lib.mrg_zero_padding(n, Fn._ptr(x, 4), -100.0, Fn._ptr(y, 4), Fn._stream()), "zero padding")
+        torch.cuda.synchronize()
+        xv = x[4:4 + n]
+        assert torch.equal(y[4:4 + n], torch.where(xv == -100.0, torch.zeros_like(xv), xv)), n
+        assert bool((y[:4] == -7.0).all()) and bool((y[4 + n:] == -7.0).all()), n
+    assert lib.mrg_zero_padding(8, Fn._ptr(x, 1), -100.0, Fn._ptr(y, 4), Fn._stream()) != 0
+    v = x[1:1022]
+    assert v.data_ptr() % 16 != 0
+    assert torch.equal(Fn.zero_padding(v), torch.where(v == -100.0, torch.zeros_like(v), v))
+    v = x[4:1025]
+    assert v.data_ptr() % 16 == 0
+    assert torch.equal(Fn.zero_padding(v), torch.where(v == -100.0, torch.zeros_like(v), v))
+
+
+def test_padding_flags_on_strided_slice():
+    """mrg_padding_flags on a [:, lead:, 2:] view of a [B, Ttot, F] tensor (batch stride Ttot F, frame stride
+    F != the view's width, a base pointer off the 16-byte grid, B T past one block and no multiple of it):
+    flags[b][t] = (view[b, t, 0] == -100) exactly; the values beside the tested column do not matter."""
+    from multimodalreactiongeneration_amd import functional as Fn
+    g = torch.Generator().manual_seed(6)
+    B, Ttot, F, lead = 7, 56, 9, 3
+    base = torch.randn(B, Ttot, F, generator=g)
+    base[torch.rand(B, Ttot, F, generator=g) < 0.3] = -100.0
+    base = base.to(DEV)
+    view = base[:, lead:, 2:]
+    assert view.stride(1) != view.shape[2] and view.data_ptr() % 16 != 0
+    flags = Fn.padding_flags(view)
+    torch.cuda.synchronize()
+    assert flags.dtype == torch.uint8 and flags.shape == (B, Ttot - lead)
+    want = (view[:, :, 0] == -100.0)
+    assert 0 < int(want.sum()) < want.numel()
+    assert torch.equal(flags.bool(), want)
+
+
+@pytest.mark.parametrize("state", [True, False], ids=["state,hT", "zero-state,no-hT"])
+@pytest.mark.parametrize("B,H,In", [(3, 16, 4), (5, 64, 40), (64, 256, 256), (2, 252, 260)])
+def test_lstm_step_fwd_vs_fp64(B, H, In, state):
+    """mrg_lstm_step_fwd called directly: the smallest shape, ragged row / unit tiles, the benchmark width
+    and In + H = 512 exactly (both K instantiations, with and without a state), h0 / c0 given or null, hT
+    given or null, y rows of stride H + 8: post-activation gates, c, y and hT vs the float64 cell at 1e-4;
+    y's padding columns untouched."""
+    from multimodalreactiongeneration_amd import _lib as L
+    from multimodalreactiongeneration_amd import functional as Fn
+    lib = L.load()
+    g = torch.Generator().manual_seed(B + H + In)
+    k = 1 / math.sqrt(H)
+    w_ih, w_hh = ((torch.rand(4 * H, n, generator=g) * 2 - 1) * k for n in (In, H))
+    b_ih, b_hh = ((torch.rand(4 * H, generator=g) * 2 - 1) * k for _ in range(2))
+    x = torch.randn(B, In, generator=g)
+    h0 = torch.randn(B, H, generator=g) if state else None
+    c0 = torch.randn(B, H, generator=g) if state else None
+    pre = x.double() @ w_ih.double().T + b_ih.double() + b_hh.double()
+    if state:
+        pre = pre + h0.double() @ w_hh.double().T
+    i_, f_, g_, o_ = pre.chunk(4, -1)
+    ref_g = torch.cat([torch.sigmoid(i_), torch.sigmoid(f_), torch.tanh(g_), torch.sigmoid(o_)], -1)
+    ref_c = torch.sigmoid(i_) * torch.tanh(g_) + (torch.sigmoid(f_) * c0.double() if state else 0)
+    ref_h = torch.sigmoid(o_) * torch.tanh(ref_c)
+    d = [None if t is None else t.to(DEV) for t in (x, h0, c0, w_ih, w_hh, b_ih, b_hh)]
+    ldy = H + 8
+    gates = torch.full((B, 4 * H), float("nan"), device=DEV)
+    c = torch.full((B, H), float("nan"), device=DEV)
+    y = torch.full((B, ldy), -7.0, device=DEV)
+    hT = torch.full((B, H), float("nan"), device=DEV) if state else None
+    L.check(lib.mrg_lstm_step_fwd(B, H, In, *[Fn._ptr(t) for t in d], Fn._ptr(gates), Fn._ptr(c), Fn._ptr(y), ldy,
+                                  Fn._ptr(hT), Fn._stream()), "lstm step fwd")
+    torch.cuda.synchronize()
+    assert rel_err(gates, ref_g) < TOL, rel_err(gates, ref_g)
+    assert rel_err(c, ref_c) < TOL, rel_err(c, ref_c)
+    assert rel_err(y[:, :H], ref_h) < TOL, rel_err(y[:, :H], ref_h)
+    assert bool((y[:, H:] == -7.0).all())
+    if state:
+        assert rel_err(hT, ref_h) < TOL and torch.equal(hT, y[:, :H])

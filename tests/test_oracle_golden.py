@@ -451,3 +451,77 @@ def test_relu_mask_injection_is_the_identity_at_the_own_kinks():
             O.run_train_step(O.metaformer_training_loss, sd, cfg["optim"], cfg["model"], batch)
     finally:
         O.RELU_MASKS = None
+
+
+def test_relu_mask_bound_rejects_a_far_flip_and_accepts_a_kink_flip():
+    """The bound the GPU checks put on injected ReLU masks (golden_util.relu_flips_ok over
+    oracle.RELU_STATS, band 1e-5 of the layer's rms, at most 32 flips) can fail: in float64 on the small
+    config, the oracle's own masks pass with 0 flips; one entry flipped at |z| > 1e-2 rms is rejected,
+    its layer's record holding exactly that flip; one entry flipped at |z| <= band rms (made by moving
+    that layer's input bias so the pre-activation lands on the kink) is accepted and counted as 1."""
+    from tests.golden_util import relu_flips_ok, relu_flip_totals
+    band = 1e-5
+    d = load("metaformer_small_r2_pad")
+    cfg = config(d)
+    sd = {k: v.double() for k, v in prefixed(d, "param/").items()}
+    batch = [(x.double(), n) for x, n in batch_from(d)]
+    real = O.relu
+
+    def own(sd_):
+        """{prefix: pre-activation} of the oracle's own forward."""
+        seen = {}
+
+        def record(x, prefix):
+            seen[prefix] = x.detach().clone()
+            return real(x, prefix)
+        O.relu = record
+        try:
+            O.metaformer_training_loss(sd_, cfg["model"], batch)
+        finally:
+            O.relu = real
+        return seen
+
+    def stats_at(sd_, masks):
+        O.RELU_MASKS, O.RELU_STATS, O.RELU_BAND = masks, {}, band
+        try:
+            O.metaformer_training_loss(sd_, cfg["model"], batch)
+            return O.RELU_STATS
+        finally:
+            O.RELU_MASKS, O.RELU_STATS, O.RELU_BAND = None, None, 1e-5
+
+    z = own(sd)
+    masks = {k: v > 0 for k, v in z.items()}
+    key = "metaformer.metaformer_blocks.0.feedforward.feed_forward.module.input."
+    assert key in z and len(z) > 1
+    st = stats_at(sd, masks)
+    assert sorted(st) == sorted(z) and all(s["n"] == z[k].numel() for k, s in st.items())
+    assert relu_flips_ok(st, band) and relu_flip_totals(st)[0] == 0
+
+    # a flip far from the kink
+    rms = z[key].pow(2).mean().sqrt().item()
+    at = int(z[key].abs().argmax())
+    zf = abs(z[key].reshape(-1)[at].item())
+    assert zf > 1e-2 * rms
+    far = {k: v.clone() for k, v in masks.items()}
+    far[key].view(-1)[at] ^= True
+    st = stats_at(sd, far)
+    assert st[key]["flips"] == 1 and st[key]["max_flip"] == zf and abs(st[key]["rms"] - rms) <= 1e-12 * rms
+    assert not relu_flips_ok(st, band)
+    assert relu_flip_totals(st)[1] >= zf / rms and relu_flip_totals(st)[0] >= 1
+
+    # a flip on the kink: move bias[j] so that entry (i, j) of this layer's pre-activation is ~0
+    j = at % z[key].shape[-1]
+    sd2 = dict(sd)
+    sd2[key + "bias"] = sd[key + "bias"].clone()
+    sd2[key + "bias"][j] -= z[key].reshape(-1)[at]
+    z2 = own(sd2)
+    rms2 = z2[key].pow(2).mean().sqrt().item()
+    assert abs(z2[key].reshape(-1)[at].item()) <= band * rms2
+    near = {k: v > 0 for k, v in z2.items()}
+    near[key].view(-1)[at] ^= True
+    st = stats_at(sd2, near)
+    assert relu_flips_ok(st, band)
+    flips, worst, where, n_near = relu_flip_totals(st)
+    assert flips == 1 and st[key]["flips"] == 1 and where == key and worst <= band and n_near >= 1
+    assert not relu_flips_ok(st, band, max_flips=0)
+    assert not relu_flips_ok({}, band)   # nothing recorded: nothing checked
