@@ -36,8 +36,18 @@ int mrg_device_cu_count(int device, int* out);
 /* ---------------------------------------------------------------- GEMM
  * C = epi(alpha * op(A) op(B) + beta * C + bias[n]); epi 0 none, 1 relu,
  * 2 multiply by (aux[m, n] > 0) (relu backward), 3 add aux[m, n] (the residual
- * branch of LN(f(x) + x): dx = g W + g without a separate add).  split-K > 1 writes fp32
- * slabs to `workspace` and reduces them in a fixed order (deterministic).
+ * branch of LN(f(x) + x): dx = g W + g without a separate add), and the smooth
+ * activations of nonlinearity / ffn_nonlinearity swish and tanh (nonlinearity.py:6-16):
+ *   4 tanh(v)                                   forward
+ *   5 v * (1 - aux^2)                           backward of 4, aux = the saved tanh output
+ *   6 silu(v) = v sigma(v), and v -> aux[m, n]  forward; the pre-activation is kept because
+ *                                               v sigma(v) is not invertible
+ *   7 v * sigma(aux) (1 + aux (1 - sigma(aux))) backward of 6, aux = the saved pre-activation
+ * (v = alpha acc + beta C + bias).  Code 6 WRITES through `aux` although the parameter is declared
+ * const (the signatures are pinned): pass a writable [M][ldaux] buffer that does not alias C.
+ * Every entry point below that takes `epilogue` takes 0..7.  split-K > 1 writes fp32
+ * slabs to `workspace` and reduces them in a fixed order (deterministic); the epilogue (and code
+ * 6's store) runs once, on the reduced sum.
  * Replaces nn.Linear / addmm (mixer_block.py:63-74, multi_modal_metaformer.py:
  * 433-435,474,504, lstm_with_sample.py:92-130) and the x W_ih^T / weight-grad
  * GEMMs inside cuDNN's LSTM (mixer_block.py:237-252).                      */
@@ -445,6 +455,14 @@ int mrg_zero_padding(long n, const float* x, float value, float* y, hipStream_t 
  * rings, loss-gradient lead frames) without a torch fill kernel.  Replaces the `zero_grad` /
  * `torch.zeros` of the reference's step (lstmformer.py:313-322 loss, Lightning's optimizer zero_grad). */
 int mrg_fill_zero(void* p, long bytes, hipStream_t stream);
+/* Elementwise activation over n floats (any alignment; 16-B accesses when every pointer is
+ * aligned): kind 1 relu, 2 tanh, 3 silu.  fwd y = act(x); bwd dx = dy * act'(saved) with saved =
+ * the post-activation (relu, tanh) or the pre-activation (silu).  The attention-output
+ * nonlinearity of MHAforSequentail (for_sequential.py:47-51); Linear -> act chains use the GEMM
+ * epilogues 4..7 instead.                                                                        */
+int mrg_activation_fwd(long n, int kind, const float* x, float* y, hipStream_t stream);
+int mrg_activation_bwd(long n, int kind, const float* dy, const float* saved, float* dx,
+                       hipStream_t stream);
 /* dst [n1][n0][E] = src [n0][n1][E] (beta = 1: dst +=): the batch-major [B, T, E] <-> time-major
  * [T, B, E] activations and gradients at the metaformer blocks' wavefront boundaries
  * (multi_modal_metaformer.py:501-502 feeds block outputs forward batch-major).  E % 4 == 0.     */

@@ -19,6 +19,7 @@
 #include <cstdlib>
 
 namespace mrg {
+MRG_EPI_NS_BEGIN
 
 // One operand tile (rows of the MFMA M or N dimension x BK) staged k-major in LDS:
 // S[k][x], x = m (or n).  TR says which index is contiguous in memory:
@@ -679,7 +680,9 @@ __global__ __launch_bounds__(1024) void colsum_final_kernel(const float* part, i
 // Host-side cap on resident blocks per CU for the persistent tile walks (0 = the occupancy the HW
 // reports).  The weight-gradient products issued beside a latency-bound recurrence run with 1, so
 // they take the CU room the recurrence leaves instead of queueing whole waves of tiles ahead of it.
-static int g_blocks_per_cu = 0;
+MRG_EPI_NS_END
+MRG_KNOB(g_blocks_per_cu, 0);
+MRG_EPI_NS_BEGIN
 
 template <typename K>
 static int resident_blocks(K kernel) {
@@ -874,28 +877,31 @@ static void launch_rows(const GemmArgs& a, hipStream_t s) {
 #undef MRG_R
 }
 
-static int g_tile_override = -1;
+MRG_EPI_NS_END
+MRG_KNOB(g_tile_override, -1);
 // LDS-DMA x6 kernel for k-contiguous products (gemm_x6g_kernel): 0 = off, else ring depth (2..4);
 // MRG_GEMM_GLDS overrides; g_glds_bn = column tile (128 or 64)
-static int g_glds = [] {
+MRG_KNOB(g_glds, [] {
   const char* e = getenv("MRG_GEMM_GLDS");
   return e ? atoi(e) : 2;
-}();
-static int g_glds_wg = [] {  // weight-gradient products on gemm_x6g_wgrad_kernel (MRG_GEMM_GLDS_WG=0: off)
+}());
+MRG_KNOB(g_glds_wg, [] {  // weight-gradient products on gemm_x6g_wgrad_kernel (MRG_GEMM_GLDS_WG=0: off)
   const char* e = getenv("MRG_GEMM_GLDS_WG");
   return e ? atoi(e) : 1;
-}();
-static int g_glds_bn = [] {  // 64 forces 64-wide column tiles (tuning); 128 = by shape
+}());
+MRG_KNOB(g_glds_bn, [] {  // 64 forces 64-wide column tiles (tuning); 128 = by shape
   const char* e = getenv("MRG_GEMM_GLDS_BN");
   return e ? atoi(e) : 128;
-}();
+}());
 
 
 // GEMM arithmetic: 1 = x6 bf16 split on the bf16 matrix cores (default), 0 = exact f32 MFMA
-static int g_gemm_mode = [] {
+MRG_KNOB(g_gemm_mode, [] {
   const char* e = getenv("MRG_GEMM_EXACT");
   return (e && atoi(e) != 0) ? 0 : 1;
-}();
+}());
+
+MRG_EPI_NS_BEGIN
 
 static int launch_gemm(int mode, const GemmArgs& a, int tile, int bk, int ta, int tb, bool va, bool vb,
                        int splits, hipStream_t s) {
@@ -926,6 +932,7 @@ static int launch_gemm(int mode, const GemmArgs& a, int tile, int bk, int ta, in
   return 0;
 }
 
+MRG_EPI_NS_END
 }  // namespace mrg
 
 using namespace mrg;
@@ -1041,8 +1048,14 @@ static int gemm_ex(int mode, int M, int N, int K, float alpha,
                    unsigned* counters, hipStream_t stream) {
   const bool mx = mode >= 1;  // bf16 matrix-core paths (x6 split or plain bf16 operands)
   MRG_REQUIRE(M >= 0 && N >= 0 && K >= 0, "mrg_gemm_f32: negative size");
-  MRG_REQUIRE(epilogue >= 0 && epilogue <= 3, "mrg_gemm_f32: bad epilogue %d", epilogue);
-  MRG_REQUIRE(epilogue < 2 || aux, "mrg_gemm_f32: epilogue %d needs aux", epilogue);
+  MRG_REQUIRE(epilogue >= 0 && epilogue <= 7, "mrg_gemm_f32: bad epilogue %d", epilogue);
+  MRG_REQUIRE(epilogue < 2 || epilogue == 4 || aux, "mrg_gemm_f32: epilogue %d needs aux", epilogue);
+#if !MRG_SMOOTH_EPI
+  if (epilogue >= 4)   // the transcendental epilogues live in the second build of these sources
+    return smooth_entry::gemm_ex(mode, M, N, K, alpha, A, transA, lda, lda_hi, a_rdiv, B, transB, ldb, ldb_hi, b_rdiv,
+                                 beta, C, ldc, bias, epilogue, aux, ldaux, workspace, splits, asum_out, asum_out2,
+                                 asum_beta, counters, stream);
+#endif
   if (M == 0 || N == 0) return 0;
   if (splits < 1) splits = 1;
   MRG_REQUIRE(splits == 1 || workspace, "mrg_gemm_f32: split-K needs workspace");
@@ -1201,7 +1214,13 @@ MRG_API int mrg_gemm_x6g_batched(int n, int M, int N, int K, float alpha, const 
                                  const float* const* bias, int epilogue, const float* const* aux, long ldaux,
                                  int bf16, hipStream_t stream) {
   MRG_REQUIRE(n >= 0 && n <= MRG_GB_MAX, "mrg_gemm_x6g_batched: n %d out of range", n);
-  MRG_REQUIRE(epilogue >= 0 && epilogue <= 3 && (epilogue < 2 || aux), "mrg_gemm_x6g_batched: bad epilogue");
+  MRG_REQUIRE(epilogue >= 0 && epilogue <= 7 && (epilogue < 2 || epilogue == 4 || aux),
+              "mrg_gemm_x6g_batched: bad epilogue");
+#if !MRG_SMOOTH_EPI
+  if (epilogue >= 4)
+    return smooth_entry::x6g_batched(n, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, epilogue, aux, ldaux, bf16,
+                                     stream);
+#endif
   if (n == 0 || M == 0 || N == 0) return 0;
   const int mode = bf16 ? 2 : g_gemm_mode;
   uintptr_t al = 0;
@@ -1276,3 +1295,23 @@ MRG_API int mrg_colsum_f32(int rows, int N, const float* X, long ld, long ld_hi,
   klaunch(colsum_final_kernel, (N + 63) / 64, 1024, 0, stream, workspace, S, N, beta, out, out2);
   return check_launch("colsum_final_kernel");
 }
+
+#if MRG_SMOOTH_EPI
+namespace mrg {
+namespace smooth_entry {
+int gemm_ex(int mode, int M, int N, int K, float alpha, const float* A, int transA, long lda, long lda_hi,
+            int a_rdiv, const float* B, int transB, long ldb, long ldb_hi, int b_rdiv, float beta, float* C,
+            long ldc, const float* bias, int epilogue, const float* aux, long ldaux, float* workspace, int splits,
+            float* asum_out, float* asum_out2, float asum_beta, unsigned* counters, hipStream_t stream) {
+  return ::gemm_ex(mode, M, N, K, alpha, A, transA, lda, lda_hi, a_rdiv, B, transB, ldb, ldb_hi, b_rdiv, beta, C, ldc,
+                   bias, epilogue, aux, ldaux, workspace, splits, asum_out, asum_out2, asum_beta, counters, stream);
+}
+int x6g_batched(int n, int M, int N, int K, float alpha, const float* const* A, long lda, const float* const* B,
+                long ldb, float beta, float* const* C, long ldc, const float* const* bias, int epilogue,
+                const float* const* aux, long ldaux, int bf16, hipStream_t stream) {
+  return ::mrg_gemm_x6g_batched(n, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, epilogue, aux, ldaux, bf16,
+                                stream);
+}
+}  // namespace smooth_entry
+}  // namespace mrg
+#endif

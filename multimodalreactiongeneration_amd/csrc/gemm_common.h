@@ -3,7 +3,46 @@
 #pragma once
 #include "mrg_common.h"
 
+// The GEMM sources (gemm.hip, gemm_glds.hip, gemm_wide.hip) are compiled twice.  The default build
+// (MRG_SMOOTH_EPI 0) knows epilogues 0..3 only, so its kernels are exactly the ones the step runs.
+// The second build (-DMRG_SMOOTH_EPI=1, build/*_smooth.o) adds the transcendental epilogues 4..7;
+// its kernels and host code live in the inline namespace mrg::smooth, its C entry points are
+// file-local, and the default build's entry points hand every call with epilogue >= 4 to it through
+// mrg::smooth_entry.  The tuning knobs (mode, tile override, ring depth ...) are defined once, in the
+// default build, and shared.
+#ifndef MRG_SMOOTH_EPI
+#define MRG_SMOOTH_EPI 0
+#endif
+#if MRG_SMOOTH_EPI
+#define MRG_EPI_NS_BEGIN inline namespace smooth {
+#define MRG_EPI_NS_END }
+#define MRG_KNOB(name, init) extern int name
+#undef MRG_API
+#define MRG_API [[maybe_unused]] static
+#else
+#define MRG_EPI_NS_BEGIN
+#define MRG_EPI_NS_END
+#define MRG_KNOB(name, init) int name = init
+#endif
+
 namespace mrg {
+namespace smooth_entry {  // defined by the MRG_SMOOTH_EPI build; arguments as the entry points of their names
+int gemm_ex(int mode, int M, int N, int K, float alpha, const float* A, int transA, long lda, long lda_hi,
+            int a_rdiv, const float* B, int transB, long ldb, long ldb_hi, int b_rdiv, float beta, float* C,
+            long ldc, const float* bias, int epilogue, const float* aux, long ldaux, float* workspace, int splits,
+            float* asum_out, float* asum_out2, float asum_beta, unsigned* counters, hipStream_t stream);
+int x6g_batched(int n, int M, int N, int K, float alpha, const float* const* A, long lda, const float* const* B,
+                long ldb, float beta, float* const* C, long ldc, const float* const* bias, int epilogue,
+                const float* const* aux, long ldaux, int bf16, hipStream_t stream);
+int x6_planes(int M, int N, int K, float alpha, const float* A, long lda, long lda_hi, int a_rdiv,
+              const void* Bplanes, long ldb, long bplane, float beta, float* C, long ldc, const float* bias,
+              int epilogue, const float* aux, long ldaux, hipStream_t stream);
+int x6_planes_batched(int n, int M, int N, int K, float alpha, const float* const* A, long lda,
+                      const void* const* Bplanes, long ldb, long bplane, float beta, float* const* C, long ldc,
+                      const float* const* bias, int epilogue, const float* const* aux, long ldaux,
+                      hipStream_t stream);
+}  // namespace smooth_entry
+MRG_EPI_NS_BEGIN
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -19,8 +58,10 @@ struct GemmArgs {
   float* C;
   long ldc;
   const float* bias;
-  int epi;  // 0 none, 1 relu, 2 multiply by (aux > 0), 3 add aux (residual gradient)
-  const float* aux;
+  int epi;  // 0 none, 1 relu, 2 multiply by (aux > 0), 3 add aux (residual gradient),
+            // 4 tanh, 5 multiply by tanh' (aux = saved tanh), 6 silu (also stores v at aux),
+            // 7 multiply by silu' (aux = saved pre-activation)
+  const float* aux;  // read by 2, 3, 5, 7; WRITTEN by 6 (the const is cast away there)
   long ldaux;
   float* ws;  // split-K slabs [splits][M][N] (nullptr when splits == 1)
   int kchunk;
@@ -48,6 +89,19 @@ struct GemmArgs {
 static constexpr int BK = 32;  // K tile (64 measured no faster here: 2 blocks/CU instead of 3)
 static constexpr int NT = 256;
 
+#if MRG_SMOOTH_EPI
+// Smooth activations and their derivatives (epilogues 4..7) on v = alpha acc + beta C + bias; x is
+// the aux element (5: saved tanh, 7: saved pre-activation; unused by 4 and 6).  Compiled only into the
+// MRG_SMOOTH_EPI build, so the kernels of the other epilogues do not carry them.
+__device__ __forceinline__ float smooth_epi(int epi, float v, float x) {
+  if (epi == 4) return tanhf_(v);
+  if (epi == 5) return v * (1.0f - x * x);
+  if (epi == 6) return v * sigmoidf_(v);
+  const float s = sigmoidf_(x);
+  return v * (s * (1.0f + x * (1.0f - s)));
+}
+#endif
+
 __device__ __forceinline__ float apply_epi(const GemmArgs& a, float v, int m, int n) {
   v *= a.alpha;
   if (a.beta != 0.0f) v += a.beta * a.C[(long)m * a.ldc + n];
@@ -55,6 +109,14 @@ __device__ __forceinline__ float apply_epi(const GemmArgs& a, float v, int m, in
   if (a.epi == 1) v = fmaxf(v, 0.0f);
   else if (a.epi == 2) v = (a.aux[(long)m * a.ldaux + n] > 0.0f) ? v : 0.0f;
   else if (a.epi == 3) v += a.aux[(long)m * a.ldaux + n];
+#if MRG_SMOOTH_EPI
+  else if (a.epi >= 4) {
+    float x = 0.0f;
+    if (a.epi == 6) const_cast<float*>(a.aux)[(long)m * a.ldaux + n] = v;
+    else if (a.epi != 4) x = a.aux[(long)m * a.ldaux + n];
+    v = smooth_epi(a.epi, v, x);
+  }
+#endif
   return v;
 }
 
@@ -89,6 +151,15 @@ __device__ __forceinline__ void store4(const GemmArgs& a, int z, int m, int n, f
       const float4 x = *reinterpret_cast<const float4*>(a.aux + (long)m * a.ldaux + n);
       o.x += x.x; o.y += x.y; o.z += x.z; o.w += x.w;
     }
+#if MRG_SMOOTH_EPI
+    else if (a.epi >= 4) {
+      float4 x = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (a.epi == 6) *reinterpret_cast<float4*>(const_cast<float*>(a.aux) + (long)m * a.ldaux + n) = o;
+      else if (a.epi != 4) x = *reinterpret_cast<const float4*>(a.aux + (long)m * a.ldaux + n);
+      o.x = smooth_epi(a.epi, o.x, x.x); o.y = smooth_epi(a.epi, o.y, x.y);
+      o.z = smooth_epi(a.epi, o.z, x.z); o.w = smooth_epi(a.epi, o.w, x.w);
+    }
+#endif
     *reinterpret_cast<float4*>(pc) = o;
     return;
   }
@@ -162,4 +233,5 @@ struct TransposeBatch {
 };
 __global__ void transpose_batched_kernel(TransposeBatch tb);
 
+MRG_EPI_NS_END
 }  // namespace mrg

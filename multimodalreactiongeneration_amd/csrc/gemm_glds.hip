@@ -3,6 +3,7 @@
 #include <cstdlib>
 
 namespace mrg {
+MRG_EPI_NS_BEGIN
 
 
 // ----------------------------------------------------------------------------------------------
@@ -564,9 +565,11 @@ __global__ __launch_bounds__(256) void transpose_batched_kernel(TransposeBatch t
   }
 }
 
+MRG_EPI_NS_END
 }  // namespace mrg
 
 namespace mrg {
+MRG_EPI_NS_BEGIN
 
 // ----------------------------------------------------------------------------------------------
 // Three bf16 planes of a weight, once per optimizer step: dst [3][R'][C'] (plane stride R' C'),
@@ -614,15 +617,20 @@ __global__ __launch_bounds__(256) void split_planes_kernel(PlaneBatch pb) {
   }
 }
 
+MRG_EPI_NS_END
 }  // namespace mrg
 
 using namespace mrg;
 
-static int g_wide_cfg = [] {
+#if MRG_SMOOTH_EPI
+extern int g_wide_cfg;
+#else
+int g_wide_cfg = [] {
   const char* e = getenv("MRG_GEMM_WIDE");
   const int v = e ? atoi(e) : 12;
   return (v == 0 || v == 22) ? v : 12;
 }();
+#endif
 
 // planes of n weights (see split_planes_kernel): dst_i holds 3 x rows_i x cols_i bf16
 MRG_API int mrg_split_planes_batched(int n, const float* const* src, void* const* dst, const int* rows, const int* cols,
@@ -657,7 +665,13 @@ MRG_API int mrg_gemm_x6_planes(int M, int N, int K, float alpha, const float* A,
                                const float* bias, int epilogue, const float* aux, long ldaux, hipStream_t stream) {
   MRG_REQUIRE(M >= 0 && N >= 0 && K >= 0, "mrg_gemm_x6_planes: negative size");
   MRG_REQUIRE(K % 32 == 0, "mrg_gemm_x6_planes: K %d not a multiple of 32", K);
-  MRG_REQUIRE(epilogue >= 0 && epilogue <= 3 && (epilogue < 2 || aux), "mrg_gemm_x6_planes: bad epilogue");
+  MRG_REQUIRE(epilogue >= 0 && epilogue <= 7 && (epilogue < 2 || epilogue == 4 || aux),
+              "mrg_gemm_x6_planes: bad epilogue");
+#if !MRG_SMOOTH_EPI
+  if (epilogue >= 4)
+    return smooth_entry::x6_planes(M, N, K, alpha, A, lda, lda_hi, a_rdiv, Bplanes, ldb, bplane, beta, C, ldc, bias,
+                                   epilogue, aux, ldaux, stream);
+#endif
   MRG_REQUIRE((((uintptr_t)A) & 15) == 0 && (lda & 3) == 0 && (a_rdiv <= 0 || (lda_hi & 3) == 0),
               "mrg_gemm_x6_planes: A rows must be 16-B aligned");
   MRG_REQUIRE((((uintptr_t)Bplanes) & 15) == 0 && (ldb & 7) == 0 && (bplane & 7) == 0,
@@ -695,7 +709,13 @@ MRG_API int mrg_gemm_x6_planes_batched(int n, int M, int N, int K, float alpha, 
                                        const float* const* aux, long ldaux, hipStream_t stream) {
   MRG_REQUIRE(n >= 1 && n <= MRG_GB_MAX && M >= 0 && N >= 0 && K >= 0 && K % 32 == 0,
               "mrg_gemm_x6_planes_batched: bad shape (n=%d, K=%d)", n, K);
-  MRG_REQUIRE(epilogue >= 0 && epilogue <= 3 && (epilogue < 2 || aux), "mrg_gemm_x6_planes_batched: bad epilogue");
+  MRG_REQUIRE(epilogue >= 0 && epilogue <= 7 && (epilogue < 2 || epilogue == 4 || aux),
+              "mrg_gemm_x6_planes_batched: bad epilogue");
+#if !MRG_SMOOTH_EPI
+  if (epilogue >= 4)
+    return smooth_entry::x6_planes_batched(n, M, N, K, alpha, A, lda, Bplanes, ldb, bplane, beta, C, ldc, bias,
+                                           epilogue, aux, ldaux, stream);
+#endif
   MRG_REQUIRE((lda & 3) == 0 && (ldb & 7) == 0 && (bplane & 7) == 0, "mrg_gemm_x6_planes_batched: alignment");
   if (M == 0 || N == 0) return 0;
   GemmArgs a;
@@ -731,3 +751,23 @@ MRG_API int mrg_gemm_set_wide(int cfg) {
     g_wide_cfg = cfg;
   return prev;
 }
+
+#if MRG_SMOOTH_EPI
+namespace mrg {
+namespace smooth_entry {
+int x6_planes(int M, int N, int K, float alpha, const float* A, long lda, long lda_hi, int a_rdiv,
+              const void* Bplanes, long ldb, long bplane, float beta, float* C, long ldc, const float* bias,
+              int epilogue, const float* aux, long ldaux, hipStream_t stream) {
+  return ::mrg_gemm_x6_planes(M, N, K, alpha, A, lda, lda_hi, a_rdiv, Bplanes, ldb, bplane, beta, C, ldc, bias,
+                              epilogue, aux, ldaux, stream);
+}
+int x6_planes_batched(int n, int M, int N, int K, float alpha, const float* const* A, long lda,
+                      const void* const* Bplanes, long ldb, long bplane, float beta, float* const* C, long ldc,
+                      const float* const* bias, int epilogue, const float* const* aux, long ldaux,
+                      hipStream_t stream) {
+  return ::mrg_gemm_x6_planes_batched(n, M, N, K, alpha, A, lda, Bplanes, ldb, bplane, beta, C, ldc, bias, epilogue,
+                                      aux, ldaux, stream);
+}
+}  // namespace smooth_entry
+}  // namespace mrg
+#endif

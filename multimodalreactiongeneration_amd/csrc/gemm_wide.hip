@@ -26,6 +26,7 @@
 #include <utility>
 
 namespace mrg {
+MRG_EPI_NS_BEGIN
 
 typedef float f32x4w __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
@@ -229,4 +230,5 @@ void launch_x6w(GemmArgs a, int bn, int ns, long bplane, hipStream_t s, const Ge
   else launch_w<128, 2>(a, bplane, s, gb);
 }
 
+MRG_EPI_NS_END
 }  // namespace mrg

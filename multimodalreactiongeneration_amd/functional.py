@@ -885,38 +885,62 @@ def _tap_relu(w1, h, lead_shape):
         RELU_TAP[w1.data_ptr()] = (h > 0).view(*lead_shape, h.shape[-1])
 
 
+# Activations of the fused feed-forward forms: name -> (forward epilogue, backward epilogue, kind of
+# mrg_activation_fwd / _bwd).  relu and tanh differentiate from the saved output h; silu's forward
+# epilogue also stores the pre-activation (GEMM epilogue 6 writes it through aux) and its
+# derivative reads that.
+ACTIVATIONS = {"relu": (1, 2, 1), "tanh": (4, 5, 2), "silu": (6, 7, 3)}
+
+
+def _act_codes(act):
+    if act not in ACTIVATIONS:
+        raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}, got {act!r}")
+    return ACTIVATIONS[act]
+
+
+def _act_fwd_gemm(M, Hb, In, x2, w1, b1, fe, dev):
+    """(h, pre): h = act(x2 w1^T + b1) by forward epilogue fe; pre = the pre-activation (silu) or None."""
+    h = torch.empty(M, Hb, device=dev, dtype=torch.float32)
+    pre = torch.empty(M, Hb, device=dev, dtype=torch.float32) if fe == 6 else None
+    gemm(M, Hb, In, _ptr(x2), 0, In, _ptr(w1), 1, In, _ptr(h), Hb, bias=_ptr(b1), epi=fe, aux=_ptr(pre),
+         ldaux=Hb if pre is not None else 0, device=dev)
+    return h, pre
+
+
 class _FFNFn(Function):
     @staticmethod
     @_keeps_precision
-    def forward(ctx, x, w1, b1, w2, b2):
+    def forward(ctx, x, w1, b1, w2, b2, act="relu"):
         _lib.require_device(x)
+        fe, ctx.be, _ = _act_codes(act)
         In, Hb, N = w1.shape[1], w1.shape[0], w2.shape[0]
         x2 = x.reshape(-1, In).contiguous()
         M = x2.shape[0]
         dev = x.device
-        h = torch.empty(M, Hb, device=dev, dtype=torch.float32)
-        gemm(M, Hb, In, _ptr(x2), 0, In, _ptr(w1), 1, In, _ptr(h), Hb, bias=_ptr(b1), epi=1, device=dev)
+        h, pre = _act_fwd_gemm(M, Hb, In, x2, w1, b1, fe, dev)
         z = torch.empty(M, N, device=dev, dtype=torch.float32)
         _fwd_gemm(M, N, Hb, _ptr(h), Hb, w2, _ptr(z), N, bias=_ptr(b2), device=dev)
         _wt_note(w1, M, ctx.needs_input_grad[0])
-        _tap_relu(w1, h, x.shape[:-1])
-        ctx.save_for_backward(x2, h, w1, b1, w2, b2)
+        if act == "relu":
+            _tap_relu(w1, h, x.shape[:-1])
+        ctx.save_for_backward(x2, h, w1, b1, w2, b2, pre)
         ctx.xshape = x.shape
         return z.view(*x.shape[:-1], N)
 
     @staticmethod
     @_keeps_precision
     def backward(ctx, dz):
-        x2, h, w1, b1, w2, b2 = ctx.saved_tensors
+        x2, h, w1, b1, w2, b2, pre = ctx.saved_tensors
         Hb, In = w1.shape
         N = w2.shape[0]
         dz2 = dz.reshape(-1, N).contiguous()
         M = dz2.shape[0]
         dev = dz.device
-        # d(pre-activation) = (dz W2) * (h > 0): relu backward fused into the GEMM epilogue
+        # d(pre-activation) = (dz W2) * act'(.): the activation's backward fused into the GEMM epilogue
+        # (relu: h > 0; tanh: 1 - h^2; silu: from the saved pre-activation)
         dh = torch.empty(M, Hb, device=dev, dtype=torch.float32)
-        gemm(M, Hb, N, _ptr(dz2), 0, N, _ptr(w2), 0, Hb, _ptr(dh), Hb, epi=2, aux=_ptr(h), ldaux=Hb,
-             device=dev)
+        gemm(M, Hb, N, _ptr(dz2), 0, N, _ptr(w2), 0, Hb, _ptr(dh), Hb, epi=ctx.be,
+             aux=_ptr(h if pre is None else pre), ldaux=Hb, device=dev)
         _wgrad(_ptr(dz2), N, _ptr(h), Hb, M, N, Hb, _gbuf(w2), dev, gb=_gbuf(b2), keep=(dz2, h))
         _wgrad(_ptr(dh), Hb, _ptr(x2), In, M, Hb, In, _gbuf(w1), dev, gb=_gbuf(b1), keep=(dh, x2))
         dx = None
@@ -924,11 +948,12 @@ class _FFNFn(Function):
             dx = torch.empty(M, In, device=dev, dtype=torch.float32)
             _dx_gemm(M, In, Hb, _ptr(dh), Hb, w1, _ptr(dx), In, device=dev)
             dx = dx.view(ctx.xshape)
-        return dx, None, None, None, None
+        return dx, None, None, None, None, None
 
 
-def ffn(x, w1, b1, w2, b2):
-    return _FFNFn.apply(x, w1, b1, w2, b2)
+def ffn(x, w1, b1, w2, b2, act="relu"):
+    """Linear -> act -> Linear, act in ACTIVATIONS (relu | tanh | silu)."""
+    return _FFNFn.apply(x, w1, b1, w2, b2, act)
 
 
 # ------------------------------------------------------------------ residual + LayerNorm
@@ -1048,33 +1073,35 @@ class _FFNResLNFn(Function):
 
     @staticmethod
     @_keeps_precision
-    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, eps):
+    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, eps, act="relu"):
         _lib.require_device(x)
+        fe, ctx.be, _ = _act_codes(act)
         Hb, E = w1.shape
         x2 = x.reshape(-1, E).contiguous()
         M = x2.shape[0]
         dev = x.device
-        h = torch.empty(M, Hb, device=dev, dtype=torch.float32)
-        gemm(M, Hb, E, _ptr(x2), 0, E, _ptr(w1), 1, E, _ptr(h), Hb, bias=_ptr(b1), epi=1, device=dev)
+        h, pre = _act_fwd_gemm(M, Hb, E, x2, w1, b1, fe, dev)
         z = torch.empty(M, E, device=dev, dtype=torch.float32)
         _fwd_gemm(M, E, Hb, _ptr(h), Hb, w2, _ptr(z), E, bias=_ptr(b2), device=dev)
         _wt_note(w1, M, ctx.needs_input_grad[0])
-        _tap_relu(w1, h, x.shape[:-1])
+        if act == "relu":
+            _tap_relu(w1, h, x.shape[:-1])
         y, mean, rstd = _resln_fwd(z, x2, gamma, beta, eps)
-        ctx.save_for_backward(x2, h, z, w1, b1, w2, b2, gamma, beta, mean, rstd)
+        ctx.save_for_backward(x2, h, z, w1, b1, w2, b2, gamma, beta, mean, rstd, pre)
         ctx.xshape = x.shape
         return y.view(x.shape)
 
     @staticmethod
     @_keeps_precision
     def backward(ctx, dy):
-        x2, h, z, w1, b1, w2, b2, gamma, beta, mean, rstd = ctx.saved_tensors
+        x2, h, z, w1, b1, w2, b2, gamma, beta, mean, rstd, pre = ctx.saved_tensors
         Hb, E = w1.shape
         M = x2.shape[0]
         dev = dy.device
         g = _resln_bwd(dy.reshape(M, E).contiguous(), z, x2, gamma, beta, mean, rstd)
         dh = torch.empty(M, Hb, device=dev, dtype=torch.float32)
-        gemm(M, Hb, E, _ptr(g), 0, E, _ptr(w2), 0, Hb, _ptr(dh), Hb, epi=2, aux=_ptr(h), ldaux=Hb, device=dev)
+        gemm(M, Hb, E, _ptr(g), 0, E, _ptr(w2), 0, Hb, _ptr(dh), Hb, epi=ctx.be,
+             aux=_ptr(h if pre is None else pre), ldaux=Hb, device=dev)
         _wgrad(_ptr(g), E, _ptr(h), Hb, M, E, Hb, _gbuf(w2), dev, gb=_gbuf(b2), keep=(g, h))
         _wgrad(_ptr(dh), Hb, _ptr(x2), E, M, Hb, E, _gbuf(w1), dev, gb=_gbuf(b1), keep=(dh, x2))
         dx = None
@@ -1082,11 +1109,143 @@ class _FFNResLNFn(Function):
             dx = torch.empty(M, E, device=dev, dtype=torch.float32)
             _dx_gemm(M, E, Hb, _ptr(dh), Hb, w1, _ptr(dx), E, epi=3, aux=_ptr(g), ldaux=E, device=dev)
             dx = dx.view(ctx.xshape)
-        return dx, None, None, None, None, None, None, None
+        return dx, None, None, None, None, None, None, None, None
 
 
-def ffn_residual_layernorm(x, w1, b1, w2, b2, gamma, beta, eps=1e-5):
-    return _FFNResLNFn.apply(x, w1, b1, w2, b2, gamma, beta, eps)
+def ffn_residual_layernorm(x, w1, b1, w2, b2, gamma, beta, eps=1e-5, act="relu"):
+    return _FFNResLNFn.apply(x, w1, b1, w2, b2, gamma, beta, eps, act)
+
+
+# ------------------------------------------------------------------ Linear -> act -> ... -> Linear
+class _MLPChainFn(Function):
+    """x -> act(W_0 x + b_0) -> ... -> W_{L-1} h + b_{L-1}: the MLP token mixer (mixer_block.py:114-166).
+    Every activation is a forward GEMM epilogue (1 / 4 / 6) and every act' is the epilogue (2 / 5 / 7)
+    of the next layer's input-gradient GEMM, so the chain runs no elementwise pass in either direction;
+    weight and bias gradients go through _wgrad, as in _FFNFn."""
+
+    @staticmethod
+    @_keeps_precision
+    def forward(ctx, x, act, *params):
+        _lib.require_device(x)
+        fe, ctx.be, _ = _act_codes(act)
+        ws, bs = params[0::2], params[1::2]
+        L = len(ws)
+        dev = x.device
+        h = x.reshape(-1, ws[0].shape[1]).contiguous()
+        M = h.shape[0]
+        hs, pres = [h], []
+        for i, (w, b) in enumerate(zip(ws, bs)):
+            N, In = w.shape
+            last = i == L - 1
+            out = torch.empty(M, N, device=dev, dtype=torch.float32)
+            pre = torch.empty(M, N, device=dev, dtype=torch.float32) if (fe == 6 and not last) else None
+            _fwd_gemm(M, N, In, _ptr(h), In, w, _ptr(out), N, bias=_ptr(b), epi=0 if last else fe,
+                      aux=_ptr(pre), ldaux=N if pre is not None else 0, device=dev)
+            _wt_note(w, M, i > 0 or ctx.needs_input_grad[0])
+            if not last:
+                hs.append(out)
+                pres.append(pre)
+            h = out
+        ctx.L = L
+        ctx.silu = fe == 6
+        ctx.save_for_backward(*hs, *(pres if ctx.silu else ()), *ws, *bs)
+        ctx.xshape = x.shape
+        return h.view(*x.shape[:-1], ws[-1].shape[0])
+
+    @staticmethod
+    @_keeps_precision
+    def backward(ctx, dy):
+        L, saved = ctx.L, ctx.saved_tensors
+        hs = saved[:L]
+        pres = saved[L:2 * L - 1] if ctx.silu else None
+        ws, bs = saved[-2 * L:-L], saved[-L:]
+        g = dy.reshape(-1, ws[-1].shape[0]).contiguous()
+        M = g.shape[0]
+        dev = dy.device
+        dx = None
+        for i in range(L - 1, -1, -1):
+            w, b = ws[i], bs[i]
+            N, In = w.shape
+            _wgrad(_ptr(g), N, _ptr(hs[i]), In, M, N, In, _gbuf(w), dev, gb=_gbuf(b), keep=(g, hs[i]))
+            if i > 0:
+                # gradient at layer i-1's pre-activation: (g W_i) * act'(.), act' in this GEMM's epilogue
+                aux = pres[i - 1] if ctx.silu else hs[i]
+                gp = torch.empty(M, In, device=dev, dtype=torch.float32)
+                _dx_gemm(M, In, N, _ptr(g), N, w, _ptr(gp), In, epi=ctx.be, aux=_ptr(aux), ldaux=In, device=dev)
+                g = gp
+            elif ctx.needs_input_grad[0]:
+                dx = torch.empty(M, In, device=dev, dtype=torch.float32)
+                _dx_gemm(M, In, N, _ptr(g), N, w, _ptr(dx), In, device=dev)
+                dx = dx.view(ctx.xshape)
+        return (dx, None) + (None,) * (2 * L)
+
+
+def mlp_chain(x, layers, act=None):
+    """layers = [(weight, bias), ...]; act (relu | tanh | silu) after every Linear but the last; None:
+    stacked linears."""
+    if act is None:
+        for w, b in layers:
+            x = linear(x, w, b)
+        return x
+    if any(b is None for _, b in layers):
+        raise NotImplementedError("mlp_chain: Linear without bias")
+    return _MLPChainFn.apply(x, act, *[t for wb in layers for t in wb])
+
+
+# ------------------------------------------------------------------ elementwise activation
+class _ActFn(Function):
+    """act(x) where no GEMM epilogue can carry it (the attention-output nonlinearity, for_sequential.py:47-51)."""
+
+    @staticmethod
+    @_keeps_precision
+    def forward(ctx, x, act):
+        _lib.require_device(x)
+        ctx.kind = _act_codes(act)[2]
+        xc = x.contiguous()
+        y = torch.empty_like(xc)
+        _lib.check(_lib.load().mrg_activation_fwd(xc.numel(), ctx.kind, _ptr(xc), _ptr(y), _stream()), "activation fwd")
+        ctx.save_for_backward(xc if ctx.kind == 3 else y)
+        return y
+
+    @staticmethod
+    @_keeps_precision
+    def backward(ctx, dy):
+        (saved,) = ctx.saved_tensors
+        dyc = dy.contiguous()
+        dx = torch.empty_like(saved)
+        _lib.check(_lib.load().mrg_activation_bwd(saved.numel(), ctx.kind, _ptr(dyc), _ptr(saved), _ptr(dx),
+                                                  _stream()), "activation bwd")
+        return dx, None
+
+
+def activation(x, act):
+    return _ActFn.apply(x, act)
+
+
+class _Sample0Fn(Function):
+    """[B, ...] -> [B, ...] with every sample replaced by sample 0 (the reference's Q7 quirk: MHAMixer
+    takes [0] of a bare tensor, and LN(y + x) broadcasts that sample over the batch).  Backward: the B
+    gradient rows summed into sample 0 (mrg_colsum_f32 over a [B, rest] view), zeros elsewhere."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _lib.require_device(x)
+        ctx.shape = x.shape
+        return x[:1].expand(x.shape).contiguous()
+
+    @staticmethod
+    @_keeps_precision
+    def backward(ctx, dy):
+        B = ctx.shape[0]
+        dyc = dy.contiguous()
+        rest = dyc.numel() // B
+        dx = zeros(*ctx.shape, device=dy.device)
+        colsum(B, rest, _ptr(dyc), rest, _ptr(dx), beta=1.0, device=dy.device)
+        return dx
+
+
+def broadcast_sample0(x):
+    return _Sample0Fn.apply(x)
 
 
 # ------------------------------------------------------------------ LSTM

@@ -59,13 +59,22 @@ def make_activation(name):
     raise ValueError("nonlinearity must be in ['relu', 'swish', 'tanh', None]")
 
 
+def activation_name(module):
+    """functional.ACTIVATIONS' name of an activation module: nn.ReLU / nn.Tanh / nn.SiLU, else None."""
+    for cls, name in ((nn.ReLU, "relu"), (nn.Tanh, "tanh"), (nn.SiLU, "silu")):
+        if isinstance(module, cls):
+            return name
+    return None
+
+
 def run_sequential_ffn(seq: nn.Sequential, x):
-    """Run an nn.Sequential of Linear [-> ReLU -> Linear] through the fused kernels."""
+    """Run an nn.Sequential of Linear [-> ReLU | SiLU | Tanh -> Linear] through the fused kernels."""
     mods = list(seq.children())
     if len(mods) == 1 and isinstance(mods[0], nn.Linear):
         return Fn.linear(x, mods[0].weight, mods[0].bias)
-    if len(mods) == 3 and isinstance(mods[1], nn.ReLU):
-        return Fn.ffn(x, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias)
+    act = activation_name(mods[1]) if len(mods) == 3 else None
+    if act is not None:
+        return Fn.ffn(x, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias, act)
     if len(mods) == 2 and all(isinstance(m, nn.Linear) for m in mods):
         return Fn.linear(Fn.linear(x, mods[0].weight, mods[0].bias), mods[1].weight, mods[1].bias)
     _unsupported(f"feed-forward {[type(m).__name__ for m in mods]}")
@@ -136,9 +145,10 @@ class FeedForward(nn.Module):
             mods = list(ff.module.children())
             if ln is not None and len(mods) == 1 and isinstance(mods[0], nn.Linear):
                 return Fn.linear_residual_layernorm(x, mods[0].weight, mods[0].bias, ln.weight, ln.bias, ln.eps)
-            if ln is not None and len(mods) == 3 and isinstance(mods[1], nn.ReLU):
+            act = activation_name(mods[1]) if (ln is not None and len(mods) == 3) else None
+            if act is not None:
                 return Fn.ffn_residual_layernorm(x, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias,
-                                                 ln.weight, ln.bias, ln.eps)
+                                                 ln.weight, ln.bias, ln.eps, act)
             return ff.combine(run_sequential_ffn(ff.module, x), x)
         return run_sequential_ffn(ff, x)
 
@@ -305,14 +315,17 @@ class MHAforSequentail(nn.Module):
         self.mha = MultiheadAttention(embed_dim, num_heads, dropout, bias, add_bias_kv, add_zero_attn,
                                       kdim, vdim, batch_first, device=device, dtype=dtype)
         self.nonlinearity = make_activation(nonlinearity)
-        if self.nonlinearity is not None:
-            _unsupported("MHA output nonlinearity (reference Q7 path)")
 
     def forward(self, x):
+        """(out, None) without a nonlinearity; with one, the BARE activated tensor, as the reference
+        returns it (MHAMixer then indexes it with [0])."""
         x = list(x)
         x[4] = False
         x[6] = False
-        return self.mha(*x)
+        out = self.mha(*x)
+        if self.nonlinearity is None:
+            return out
+        return Fn.activation(out[0], activation_name(self.nonlinearity))
 
 
 class LSTMSampler(nn.Module):

@@ -124,6 +124,8 @@ class IntegrateModalBlock(nn.Module):
             res, ffw = blk.mixer, getattr(blk.feed_forward, "feed_forward", None)
             if not (isinstance(res, ResidualConnection) and res.layer_norm is not None and len(res.module.mixer) == 1):
                 return None
+            if res.module.mixer[0].nonlinearity is not None:   # Q7: the module path mirrors it
+                return None
             mha = res.module.mixer[0].mha
             if (not mha.batch_first or (mha.dropout and mha.training) or mha.in_proj_bias is None
                     or tuple(mha.in_proj_weight.shape) != (3 * E, E) or mha.out_proj.bias is None
@@ -271,6 +273,9 @@ class MultiModalMetaformer(nn.Module):
             [ResidualConnection(b, interlayer_residual_norm, hidden_dim) if interlayer_residual else b
              for b in blocks])
         self.output_feedforward = FeedForward(**output_feedforward_configs)
+        if self._module_path_only():
+            for b in blocks:   # every fused schedule declines such a model, the integrator's too
+                b.integrator.use_fused = False
 
     # ---- MI355X schedule for the first block's embedding (batched recurrences)
     def _fast_first_embedding(self, block: MultiModalMetaformerBlock, mods: List[torch.Tensor]):
@@ -356,8 +361,22 @@ class MultiModalMetaformer(nn.Module):
             return None
         return encoder_stack([(f, e.weight, e.bias, l) for f, e, l in zip(feats, embs, layers)], eps)
 
+    def _module_path_only(self) -> bool:
+        """True when the model holds what only the module path runs: an MLP mixer, a swish / tanh
+        activation (FeedForward or mixer), or an attention with an output nonlinearity (Q7).  The
+        module tree is fixed after construction, so the scan runs once."""
+        got = self.__dict__.get("_module_path_only_cached")
+        if got is None:
+            from .layers import MHAforSequentail
+            from .mixers import MLPMixer
+            got = any(isinstance(m, (MLPMixer, nn.SiLU, nn.Tanh))
+                      or (isinstance(m, MHAforSequentail) and m.nonlinearity is not None)
+                      for m in self.modules())
+            self.__dict__["_module_path_only_cached"] = got
+        return got
+
     def _fast_eligible(self) -> bool:
-        if self.interlayer_residual:
+        if self.interlayer_residual or self._module_path_only():
             return False
         for block in self.metaformer_blocks:
             for lay in block.embedding.modal_embeddings:

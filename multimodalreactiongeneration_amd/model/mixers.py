@@ -3,8 +3,13 @@
 Same constructor arguments, module attribute names and forward tuple
 conventions as the reference (nn.Sequential-friendly tuples, the
 ``split_state`` state plumbing), so configs and checkpoints carry over.
-LSTM, GRU and MHA mixers run on libmrg.so.  The MLP mixer is outside the
-benchmarked path (unused by the BASELINE configs) and raises.
+LSTM, GRU, MHA and MLP mixers run on libmrg.so.  The MLP mixer is a Linear ->
+act chain whose activations and their derivatives are GEMM epilogues
+(functional.mlp_chain).  With a ``nonlinearity`` the attention mixer mirrors
+the reference's Q7 behaviour: the activated attention output of SAMPLE 0 is
+what every sample's residual LayerNorm receives (MHAMixer.forward).  Models
+with MLP blocks, swish / tanh FeedForwards or an attention nonlinearity run
+module by module; the fused schedules decline them (metaformer._fast_eligible).
 """
 from __future__ import annotations
 
@@ -15,7 +20,8 @@ import torch
 from torch import nn
 
 from .. import functional as Fn
-from .layers import GRU, LSTM, MHAforSequentail, ResidualConnection, FeedForward
+from .layers import GRU, LSTM, Linear, MHAforSequentail, ResidualConnection, FeedForward, activation_name, \
+    make_activation
 
 
 def split_state(state, prev_state):
@@ -87,7 +93,7 @@ class MHAMixer(Mixer):
     def fused_residual_ln(self, ln, q, k, v, attn_mask=None):
         """LN(MHA(q, k, v) + q) in one op (single layer, batch_first, k is v, reference mask)."""
         from .masks import BlockCausalMask
-        if len(self.mixer) != 1 or k is not v:
+        if len(self.mixer) != 1 or k is not v or self.mixer[0].nonlinearity is not None:
             return None
         mha = self.mixer[0].mha
         if not mha.batch_first or (mha.dropout and mha.training):
@@ -105,12 +111,52 @@ class MHAMixer(Mixer):
         if len(self.mixer) > 1:
             raise NotImplementedError("MHAMixer num_layers > 1 (reference feeds a tuple into layer 2)")
         x = (q, k, v, None, False, attn_mask, False, False)
-        return self.mixer[0](x)[0]
+        out = self.mixer[0](x)
+        if isinstance(out, torch.Tensor):
+            # Q7 (for_sequential.py:47-51, mixer_block.py:300-305): with a nonlinearity the layer returns
+            # a bare [B, T, E] tensor and the reference's [0] picks SAMPLE 0, which its residual
+            # LN(y + x) then broadcasts over the batch; returned here already broadcast
+            if not self.mixer[0].mha.batch_first:
+                raise NotImplementedError("MHAMixer nonlinearity with batch_first=False")
+            return Fn.broadcast_sample0(out)
+        return out[0]
 
 
 class MLPMixer(Mixer):
-    def __init__(self, *a, **k):
-        raise NotImplementedError("MLP mixer is outside the MI355X path (not in the BASELINE configs)")
+    """Linear [-> act] x num_layer -> Linear token mixer (mixer_block.py:114-166).  The reference
+    registers the input / last hidden / output blocks both as attributes and inside ``mixer``, and with
+    num_layer > 2 overwrites ``hidden_block`` in its loop (only the last one keeps that name); the
+    state_dict keys follow."""
+
+    def __init__(self, input_size: int, hidden_size: int, num_layer: int = 1, nonlinearity=None,
+                 bias: bool = True, device=None, dtype=None):
+        super().__init__()
+        if num_layer < 1:
+            raise ValueError("num_layer must be greater than 0.")
+        conf = {"bias": bias, "device": device, "dtype": dtype}
+        self.act = activation_name(make_activation(nonlinearity))
+
+        def stage(name, n_in):
+            seq = nn.Sequential()
+            seq.add_module(name, Linear(n_in, hidden_size, **conf))
+            if self.act is not None:
+                seq.add_module("activation", make_activation(nonlinearity))
+            return seq
+        self.input_block = stage("input", input_size)
+        hidden = []
+        for _ in range(1, num_layer):
+            self.hidden_block = stage("hidden", hidden_size)
+            hidden.append(self.hidden_block)
+        self.output_block = Linear(hidden_size, hidden_size, **conf)
+        self.mixer = nn.Sequential()
+        self.mixer.add_module("input", self.input_block)
+        for i, blk in enumerate(hidden):
+            self.mixer.add_module(f"hidden[{i + 1}]", blk)
+        self.mixer.add_module("output", self.output_block)
+
+    def forward(self, x):
+        linears = [m[0] if isinstance(m, nn.Sequential) else m for m in self.mixer]
+        return Fn.mlp_chain(x, [(l.weight, l.bias) for l in linears], self.act)
 
 
 class GRUMixer(Mixer):
@@ -161,6 +207,23 @@ class LSTMMixerBlock(MixerBlock):
         y = self.feed_forward(y)
         prev_hx.append(first)
         return (y, hx, prev_hx)
+
+
+class MLPMixerBlock(MixerBlock):
+    """Residual MLP mixer + FeedForward; tensor in, tensor out (mixer_block.py:308-352)."""
+
+    def __init__(self, hidden_size: int, num_layer: int = 1, nonlinearity=None, residual: bool = False,
+                 residual_layer_norm: bool = False, bottleneck_size: int = None, bias: bool = True,
+                 device=None, dtype=None):
+        super().__init__()
+        self.mixer = MLPMixer(hidden_size, hidden_size, num_layer, nonlinearity, bias, device, dtype)
+        if residual:
+            self.mixer = ResidualConnection(self.mixer, residual_layer_norm, hidden_size)
+        self.feed_forward = FeedForward(hidden_size, bottleneck_size, None, nonlinearity, residual,
+                                        residual_layer_norm, bias, device, dtype)
+
+    def forward(self, x):
+        return self.feed_forward(self.mixer(x))
 
 
 class GRUMixerBlock(MixerBlock):
@@ -311,9 +374,31 @@ class MHAMixerLayerd(_Layerd):
         return (query, hx, (key, value, attn_mask))
 
 
-class MLPMixerLayerd(MixerLayerd):
-    def __init__(self, *a, **k):
-        raise NotImplementedError("MLP mixer is outside the MI355X path (not in the BASELINE configs)")
+class MLPMixerLayerd(_Layerd):
+    """num_layerd MLPMixerBlocks named block[i]; hx and other pass through (mixer_block.py:606-676)."""
+
+    def __init__(self, hidden_size: int, input_projection: bool = False, input_projection_size: int = None,
+                 output_projection: bool = False, output_projection_size: int = None, num_layerd: int = 1,
+                 num_internal_layer: int = 1, nonlinearity=None, residual: bool = False,
+                 residual_layer_norm: bool = False, bottleneck_size: int = None, bias: bool = True,
+                 device=None, dtype=None):
+        super().__init__()
+        self._projections(hidden_size, input_projection, input_projection_size, output_projection,
+                          output_projection_size, bias)
+        self.mixer = nn.Sequential()
+        for i in range(num_layerd):
+            self.mixer.add_module(f"block[{i + 1}]", MLPMixerBlock(
+                hidden_size, num_internal_layer, nonlinearity, residual, residual_layer_norm, bottleneck_size,
+                bias, device, dtype))
+
+    def forward(self, x, hx=None, other=(None,)):
+        if self.input_projection is not None:
+            x = self.input_projection(x)
+        for block in self.mixer:
+            x = block(x)
+        if self.output_projection is not None:
+            x = self.output_projection(x)
+        return (x, hx, other)
 
 
 class GRUMixerLayerd(_Layerd):
@@ -344,7 +429,7 @@ class GRUMixerLayerd(_Layerd):
         return (x, hx, other)
 
 
-_BLOCKS = {"mlp": None, "gru": GRUMixerBlock, "lstm": LSTMMixerBlock, "mha": MHAMixerBlock}
+_BLOCKS = {"mlp": MLPMixerBlock, "gru": GRUMixerBlock, "lstm": LSTMMixerBlock, "mha": MHAMixerBlock}
 _LAYERDS = {"mlp": MLPMixerLayerd, "gru": GRUMixerLayerd, "lstm": LSTMMixerLayerd, "mha": MHAMixerLayerd}
 
 
@@ -352,10 +437,7 @@ class MixerBlockFactory:
     def build(self, mixer_type, configs):
         if mixer_type not in _BLOCKS:
             raise ValueError(f"mixer_type must be in {list(_BLOCKS)}.")
-        cls = _BLOCKS[mixer_type]
-        if cls is None:
-            raise NotImplementedError(f"{mixer_type} mixer is outside the MI355X path")
-        return cls(**configs)
+        return _BLOCKS[mixer_type](**configs)
 
 
 class MixerLayerdFactory:
@@ -372,9 +454,7 @@ def _accepted(cls):
 _LAYERD_ARGS = {
     "lstm": _accepted(LSTMMixerLayerd), "mha": _accepted(MHAMixerLayerd),
     "gru": _accepted(GRUMixerLayerd),
-    "mlp": ["hidden_size", "input_projection", "input_projection_size", "output_projection",
-            "output_projection_size", "num_layerd", "num_internal_layer", "nonlinearity", "residual",
-            "residual_layer_norm", "bottleneck_size", "bias", "device", "dtype"],
+    "mlp": _accepted(MLPMixerLayerd),
 }
 
 
@@ -383,10 +463,8 @@ def mixer_layerd_argments_select(mixer_type: str, hidden_size: int, **kw) -> dic
     if mixer_type not in _LAYERD_ARGS:
         raise ValueError(f"mixer_type must be in {list(_LAYERD_ARGS)}")
     cls = _LAYERDS[mixer_type]
-    defaults = {}
-    if mixer_type in ("lstm", "mha", "gru"):
-        defaults = {k: v.default for k, v in inspect.signature(cls.__init__).parameters.items()
-                    if k != "self" and v.default is not inspect.Parameter.empty}
+    defaults = {k: v.default for k, v in inspect.signature(cls.__init__).parameters.items()
+                if k != "self" and v.default is not inspect.Parameter.empty}
     out = {k: defaults.get(k) for k in _LAYERD_ARGS[mixer_type]}
     out["hidden_size"] = hidden_size
     for k, v in kw.items():
