@@ -402,6 +402,48 @@ int mrg_attention_bwd_chunk(int B, int heads, int Tq, int Tk, int D, int q_off, 
                             float* dv, long dv_bs, long dv_ts, int passes, int kv_accumulate,
                             float* workspace, hipStream_t stream);
 
+/* ---------------------------------------------------------------- dropout RNG
+ * Counter-based and graph-safe (csrc/rng.h; host restatement rng.py).  Generator: Philox4x32-10.
+ * state: two uint64 in device memory, {seed, draw}.  mrg_rng_draw is a one-thread kernel that copies
+ * {seed, draw} into key_out (two uint64, owned by the calling op) and advances draw by 1 with an
+ * atomic add, so two streams never take the same draw and a replayed HIP graph takes fresh draws.
+ * Every kernel below reads `key` from device memory.  Keep rule: keep iff word >= thr, with
+ * thr = floor(p * 2^32) computed by the caller in double (p in [0, 1)) and scale_keep = 1 / (1 - p).
+ * Index map, Philox key (lo32(seed), hi32(seed) ^ hi32(draw)):
+ *   flat element i            counter (lo32(i >> 2), hi32(i >> 2), 0xFFFFFFFF, lo32(draw)), word i & 3
+ *   attention (b, head, q, k) counter (k >> 2, q, b * heads + head, lo32(draw)),            word k & 3
+ * mrg_dropout: y[i] = keep(i) ? x[i] * scale_keep : 0 over n floats (nn.LSTM / nn.GRU inter-layer
+ * dropout, mixer_block.py:169-252; the backward is the same call on the gradient with the saved key).
+ * mrg_dropout_keep_mask / mrg_attention_keep_mask write the keep decisions as uint8 (out [n] /
+ * [B, heads, Tq, Tk]; Tq and B * heads at most 65535) for tests and debugging.                      */
+int mrg_rng_draw(unsigned long long* state, unsigned long long* key_out, hipStream_t stream);
+int mrg_dropout(long n, unsigned int thr, float scale_keep, const unsigned long long* key, const float* x,
+                float* y, hipStream_t stream);
+int mrg_dropout_keep_mask(long n, unsigned int thr, const unsigned long long* key, unsigned char* out,
+                          hipStream_t stream);
+int mrg_attention_keep_mask(int B, int heads, int Tq, int Tk, unsigned int thr,
+                            const unsigned long long* key, unsigned char* out, hipStream_t stream);
+/* mrg_attention_fwd / mrg_attention_bwd with dropout on the attention probabilities
+ * (nn.MultiheadAttention(dropout = p) in training, for_sequential.py:27-51): the softmax statistics
+ * and lse use the undropped P; O = (P o keep / (1 - p)) V; backward dV += (P o keep / (1 - p))^T dO,
+ * dP = (dO V^T) o keep / (1 - p), dS = P o (dP - delta) with delta = rowsum(P o dP) formed by the dQ pass
+ * (equal to rowsum(dO o O); see attention.hip).  The backward is always the two-pass
+ * form (the workspace is used), and must be given the key its forward used.                        */
+int mrg_attention_fwd_dropout(int B, int heads, int Tq, int Tk, int D,
+                              const float* q, long q_bs, long q_ts, const float* k, long k_bs, long k_ts,
+                              const float* v, long v_bs, long v_ts, float* o, long o_bs, long o_ts,
+                              float* lse, const unsigned char* qpad, const unsigned char* kpad,
+                              int causal, float scale, unsigned int thr, float scale_keep,
+                              const unsigned long long* key, hipStream_t stream);
+int mrg_attention_bwd_dropout(int B, int heads, int Tq, int Tk, int D,
+                              const float* q, long q_bs, long q_ts, const float* k, long k_bs, long k_ts,
+                              const float* v, long v_bs, long v_ts, const float* o, long o_bs, long o_ts,
+                              const float* lse, const unsigned char* qpad, const unsigned char* kpad,
+                              int causal, float scale, const float* dout, long do_bs, long do_ts,
+                              float* dq, long dq_bs, long dq_ts, float* dk, long dk_bs, long dk_ts,
+                              float* dv, long dv_bs, long dv_ts, float* workspace, unsigned int thr,
+                              float scale_keep, const unsigned long long* key, hipStream_t stream);
+
 /* ---------------------------------------------------------------- LayerNorm
  * y = LayerNorm(a + b) (ResidualConnection.forward, residual_connection.py:
  * 20-37), rows x E, 1 <= E <= 1024; mean/rstd saved per row.     */

@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("MRG_LIB_PATH", os.path.join(_HERE, "libmrg.so"))
 
 c_int, c_long, c_float, c_size, c_void = (ctypes.c_int, ctypes.c_long, ctypes.c_float,
                                           ctypes.c_size_t, ctypes.c_void_p)
+c_uint = ctypes.c_uint32
 P = ctypes.c_void_p
 PP = ctypes.POINTER(ctypes.c_void_p)
 PL = ctypes.POINTER(ctypes.c_long)
@@ -111,6 +112,18 @@ SIGNATURES = {
                                         P, c_long, c_long, P, P, P, c_int, c_float,
                                         P, c_long, c_long, P, c_long, c_long, P, c_long, c_long,
                                         P, c_long, c_long, c_int, c_int, P, P]),
+    "mrg_rng_draw": (c_int, [P, P, P]),
+    "mrg_dropout": (c_int, [c_long, c_uint, c_float, P, P, P, P]),
+    "mrg_dropout_keep_mask": (c_int, [c_long, c_uint, P, P, P]),
+    "mrg_attention_keep_mask": (c_int, [c_int, c_int, c_int, c_int, c_uint, P, P, P]),
+    "mrg_attention_fwd_dropout": (c_int, [c_int, c_int, c_int, c_int, c_int,
+                                          P, c_long, c_long, P, c_long, c_long, P, c_long, c_long,
+                                          P, c_long, c_long, P, P, P, c_int, c_float, c_uint, c_float, P, P]),
+    "mrg_attention_bwd_dropout": (c_int, [c_int, c_int, c_int, c_int, c_int,
+                                          P, c_long, c_long, P, c_long, c_long, P, c_long, c_long,
+                                          P, c_long, c_long, P, P, P, c_int, c_float,
+                                          P, c_long, c_long, P, c_long, c_long, P, c_long, c_long,
+                                          P, c_long, c_long, P, c_uint, c_float, P, P]),
     "mrg_residual_layernorm_fwd": (c_int, [c_int, c_int, P, P, P, P, c_float, P, P, P, P]),
     "mrg_residual_layernorm_bwd_workspace_bytes": (c_size, [c_int, c_int]),
     "mrg_residual_layernorm_bwd": (c_int, [c_int, c_int, P, P, P, P, P, P, P, P, P, c_int, P, P]),

@@ -25,6 +25,7 @@
 // also forms delta = rowsum(dO * O) for its rows) and then a dK/dV kernel per
 // 64-key block, both recomputing P from the forward's log-sum-exp.
 #include "mrg_common.h"
+#include "rng.h"
 
 namespace mrg {
 
@@ -56,7 +57,17 @@ struct AttnArgs {
   // lse / delta rows: [B, Hh, st_ld] arrays, this call's queries at column st_off (chunk calls hand in
   // the whole sequence's statistics: st_ld = Tqf, st_off = q_off)
   int st_ld, st_off;
+  // attention-probability dropout (the DROP instantiations only; rng.h): the op's 16-byte key in
+  // device memory, the keep threshold and 1 / (1 - p)
+  const unsigned long long* rkey;
+  uint32_t thr;
+  float keep_scale;
 };
+
+// word `i` (0..3) of a Philox result, as selects (a dynamic index would spill the four words)
+__device__ __forceinline__ uint32_t philox_word(const Philox4& w, int i) {
+  return i == 0 ? w.w[0] : i == 1 ? w.w[1] : i == 2 ? w.w[2] : w.w[3];
+}
 
 __device__ __forceinline__ long stat_row(const AttnArgs& a, int b, int h, int qi) {
   return ((long)b * a.Hh + h) * a.st_ld + a.st_off + qi;
@@ -250,7 +261,11 @@ __device__ __forceinline__ f32x4 qk16(const float* Ks, int rowbase, const float 
   return s0 + s1;
 }
 
-template <int D>
+// DROP: dropout on the attention probabilities (nn.MultiheadAttention(dropout=p) in training).  The
+// online-softmax max / sum and the stored log-sum-exp use the undropped probabilities; the P.V
+// product uses P o keep / (1 - p).  A lane's four accumulator registers of a sub-tile are four
+// consecutive keys of one query: one Philox call (rng.h attn_words) feeds them.
+template <int D, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
   using C = AttnCfg<D>;
   __shared__ __attribute__((aligned(16))) float Ks[TT * C::SA];
@@ -267,6 +282,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
   const int kmax = key_bound(a, qi);                    // this lane's query
   const int wmin = key_bound(a, q0 + wave * 16);        // smallest bound in the wave (monotone in i)
   const int wlim = key_bound(a, q0 + wave * 16 + 15);   // largest: sub-tiles from here on are masked
+  DropKey dkey = {};
+  if constexpr (DROP) dkey = load_drop_key(a.rkey);
 
   float qreg[C::KS];
   if (a.qvec) {
@@ -352,6 +369,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         if (h == 1 && !two) break;
+        if constexpr (DROP) {
+          const Philox4 w = attn_words(dkey, (uint32_t)(b * a.Hh + blockIdx.x), (uint32_t)(a.q_off + qi),
+                                       (uint32_t)((kb + 16 * h) / 4 + lg));
+#pragma unroll
+          for (int r = 0; r < 4; ++r) p[4 * h + r] = w.w[r] >= a.thr ? p[4 * h + r] * a.keep_scale : 0.0f;
+        }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
           float vv[C::DT];
@@ -376,7 +399,18 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
 //
 // dQ for 64 queries of one (b, head): recompute P^T, dP^T = V dO^T, dS^T, dQ^T += K^T dS^T.
 // Also forms delta = rowsum(dO * O) for these rows (the dK/dV kernel reads it from a.dlt).
-template <int D>
+// DROP: dP = (dO V^T) o keep / (1 - p), and delta is formed HERE as rowsum(P o dP), the same quantity as
+// rowsum(dO * O) but made of the very terms it is subtracted from: the kernel accumulates
+// A = (P o dP)^T K and B = P^T K over the keys and writes dQ = A - delta B, so the parts of dS that cancel
+// in exact arithmetic (all of it for a row with one visible key) cancel in fp32 too.  S is formed as the
+// forward forms it (qk16), so P is bitwise the forward's.
+__device__ __forceinline__ float sub_product(float acc, float x, float y) {
+#pragma clang fp contract(off)   // acc - round(x y): a fused multiply-add would keep the product's rounding error
+  const float m = x * y;
+  return acc - m;
+}
+
+template <int D, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
   using C = AttnCfg<D>;
   constexpr int ST = 1;  // 16-row sub-tiles per step (2 measured no faster)
@@ -393,6 +427,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
   const bool qp = pad && qv && a.qpad[(long)b * a.qp_bs + qi];
   const int kmax = key_bound(a, qi);
   const int wlim = key_bound(a, q0 + wave * 16 + 15);
+  DropKey dkey = {};
+  if constexpr (DROP) dkey = load_drop_key(a.rkey);
   float qreg[C::KS], dreg[C::KS];
   float dsum = 0.0f;
   row_values<D>(a.q + (long)b * a.q_bs + (long)min(qi, a.Tq - 1) * a.q_ts + hoff, lg, qv, qreg);
@@ -414,10 +450,16 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
   const long rowi = stat_row(a, b, h, qi);
   const float lse = qv ? a.lse[rowi] : 0.0f;
   const float dl = dsum;
-  if (qv && lg == 0) a.dlt[rowi] = dsum;
+  if (!DROP && qv && lg == 0) a.dlt[rowi] = dsum;
   f32x4 dq[C::DT];
+  f32x4 bq[DROP ? C::DT : 1];   // DROP: B = P^T K
+  float dacc = 0.0f;            // DROP: this lane's share of delta = rowsum(P o dP)
 #pragma unroll
   for (int dt = 0; dt < C::DT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if constexpr (DROP) {
+#pragma unroll
+    for (int dt = 0; dt < C::DT; ++dt) bq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
   const int klim = key_bound(a, q0 + 63);
   const float* kb_ = a.k + (long)b * a.k_bs + hoff;
   const float* vb_ = a.v + (long)b * a.v_bs + hoff;
@@ -460,20 +502,38 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
         for (int s = 0; s < C::KS; ++s)
 #pragma unroll
           for (int u = 0; u < ST; ++u) {
-            s4[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(kk[u][s], qreg[s], s4[u], 0, 0, 0);
+            if constexpr (!DROP) s4[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(kk[u][s], qreg[s], s4[u], 0, 0, 0);
             dp4[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(vv[u][s], dreg[s], dp4[u], 0, 0, 0);
           }
+        if constexpr (DROP) {
+#pragma unroll
+          for (int u = 0; u < ST; ++u) s4[u] = qk16<D>(Ks, (sub + u) * 16, qreg, lq, lg);
+        }
       }
       float ds[ST][4];
+      float pw[ST][4];   // DROP: the undropped probabilities (B's operand)
 #pragma unroll
-      for (int u = 0; u < ST; ++u)
+      for (int u = 0; u < ST; ++u) {
+        if constexpr (DROP) {
+          const Philox4 w = attn_words(dkey, (uint32_t)(b * a.Hh + h), (uint32_t)(a.q_off + qi),
+                                       (uint32_t)((kb + 16 * u) / 4 + lg));
+#pragma unroll
+          for (int r = 0; r < 4; ++r) dp4[u][r] = w.w[r] >= a.thr ? dp4[u][r] * a.keep_scale : 0.0f;
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int kl = (sub + u) * 16 + lg * 4 + r;
           const bool vis = qv && (k0 + kl < kmax) && !((qmask >> kl) & 1ull);
           const float e = __expf(s4[u][r] - lse);
-          ds[u][r] = (vis ? e : 0.0f) * (dp4[u][r] - dl);
+          if constexpr (DROP) {
+            pw[u][r] = vis ? e : 0.0f;
+            ds[u][r] = pw[u][r] * dp4[u][r];
+            dacc += ds[u][r];
+          } else {
+            ds[u][r] = (vis ? e : 0.0f) * (dp4[u][r] - dl);
+          }
         }
+      }
 #pragma unroll
       for (int u = 0; u < ST; ++u) {
         if (u == 1 && !two) break;
@@ -482,11 +542,23 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
           float kk[C::DT];
           col_operands<D, C::SA>(Ks, (sub + u) * 16 + 4 * lg + s, lq, kk);
 #pragma unroll
-          for (int dt = 0; dt < C::DT; ++dt)
+          for (int dt = 0; dt < C::DT; ++dt) {
             dq[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kk[dt], ds[u][s], dq[dt], 0, 0, 0);
+            if constexpr (DROP) bq[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kk[dt], pw[u][s], bq[dt], 0, 0, 0);
+          }
         }
       }
     }
+  }
+  if constexpr (DROP) {
+    // every accumulator register of this lane belongs to query qi (column lq of the products)
+    dacc += __shfl_xor(dacc, 16, 64);
+    dacc += __shfl_xor(dacc, 32, 64);
+    if (qv && lg == 0) a.dlt[rowi] = dacc;
+#pragma unroll
+    for (int dt = 0; dt < C::DT; ++dt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dq[dt][r] = sub_product(dq[dt][r], dacc, bq[dt][r]);
   }
   if (qv) {
     float* op = a.dq + (long)b * a.dq_bs + (long)qi * a.dq_ts + hoff;
@@ -502,7 +574,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs a) {
 
 // dK, dV for 64 keys of one (b, head): S = Q K^T (query rows), P, dP = dO V^T,
 // dV^T += dO^T P, dK^T += Q^T dS
-template <int D>
+// DROP: dV += (P o keep / (1 - p))^T dO and dP = (dO V^T) o keep / (1 - p).  Here a lane holds ONE key
+// and four consecutive queries, so its four registers sit in four different Philox counters (the
+// counter runs over keys): four calls per sub-tile, one word used of each.
+template <int D, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
   using C = AttnCfg<D>;
   constexpr int ST = 1;
@@ -521,6 +596,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
   const bool kp = pad && kv && a.kpad[(long)b * a.Tk + kj];
   const int qmin = query_start(a, kj);
   const int wq0 = query_start(a, min(kb0 + wave * 16, a.Tk - 1));
+  DropKey dkey = {};
+  if constexpr (DROP) dkey = load_drop_key(a.rkey);
   float kreg[C::KS], vreg[C::KS];
   row_values<D>(a.k + (long)b * a.k_bs + (long)min(kj, a.Tk - 1) * a.k_ts + hoff, lg, kv, kreg);
   row_values<D>(a.v + (long)b * a.v_bs + (long)min(kj, a.Tk - 1) * a.v_ts + hoff, lg, kv, vreg);
@@ -599,7 +676,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
           const bool vis = kv && qq >= qmin && qq < a.Tq && !((kmask >> (qr + r)) & 1ull);
           const float e = __expf(s4[u][r] * a.scale - lv[r]);
           p[u][r] = vis ? e : 0.0f;
-          ds[u][r] = p[u][r] * (dp4[u][r] - dv[r]);
+          if constexpr (DROP) {
+            const Philox4 w = attn_words(dkey, (uint32_t)(b * a.Hh + h), (uint32_t)(a.q_off + qq), (uint32_t)(kj >> 2));
+            const float km = philox_word(w, kj & 3) >= a.thr ? a.keep_scale : 0.0f;
+            ds[u][r] = p[u][r] * (dp4[u][r] * km - dv[r]);
+            p[u][r] *= km;   // the dV product's operand
+          } else {
+            ds[u][r] = p[u][r] * (dp4[u][r] - dv[r]);
+          }
         }
       }
 #pragma unroll
@@ -974,6 +1058,77 @@ MRG_API int mrg_attention_bwd(int B, int Hh, int Tq, int Tk, int D,
   dim3 gk(Hh, B, (Tk + 63) / 64);
   MRG_ATTN_DISPATCH(attn_bwd_dkv_kernel, gk, a);
   return check_launch("attn_bwd_dkv_kernel");
+}
+
+// Attention-probability dropout (nn.MultiheadAttention(dropout = p) in training): the DROP
+// instantiations of the forward and of the two-pass backward.  The single-pass backward and the
+// chunk forms have no dropout variant, so the dispatcher never picks them here.
+#define MRG_ATTN_DISPATCH_DROP(KERNEL, grid, args)                           \
+  switch (D) {                                                               \
+    case 8: klaunch(KERNEL<8, true>, grid, 256, 0, stream, args); break;     \
+    case 16: klaunch(KERNEL<16, true>, grid, 256, 0, stream, args); break;   \
+    case 32: klaunch(KERNEL<32, true>, grid, 256, 0, stream, args); break;   \
+    case 64: klaunch(KERNEL<64, true>, grid, 256, 0, stream, args); break;   \
+  }
+
+static int drop_check(unsigned int thr, float scale_keep, const unsigned long long* key, int B, int Hh) {
+  MRG_REQUIRE(key != nullptr && (((uintptr_t)key) & 7) == 0, "attention dropout: key (2 x uint64, 8-B aligned) required");
+  MRG_REQUIRE(scale_keep >= 1.0f && std::isfinite(scale_keep), "attention dropout: scale_keep = 1 / (1 - p), p in [0, 1)");
+  MRG_REQUIRE((long)B * Hh < 0xFFFFFFFFL, "attention dropout: B * heads too large");
+  (void)thr;
+  return 0;
+}
+
+MRG_API int mrg_attention_fwd_dropout(int B, int Hh, int Tq, int Tk, int D,
+                                      const float* q, long q_bs, long q_ts, const float* k, long k_bs, long k_ts,
+                                      const float* v, long v_bs, long v_ts, float* o, long o_bs, long o_ts,
+                                      float* lse, const unsigned char* qpad, const unsigned char* kpad,
+                                      int causal, float scale, unsigned int thr, float scale_keep,
+                                      const unsigned long long* key, hipStream_t stream) {
+  if (int e = attn_check(D, Tq, Tk, causal)) return e;
+  if (int e = drop_check(thr, scale_keep, key, B, Hh)) return e;
+  if (B == 0 || Tq == 0) return 0;
+  MRG_REQUIRE(rows16(k, k_bs, k_ts) && rows16(v, v_bs, v_ts),
+              "attention fwd: K/V rows must be 16-B aligned (strides multiple of 4 floats)");
+  AttnArgs a = attn_base(B, Hh, Tq, Tk, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse,
+                         qpad, kpad, causal, scale);
+  a.qvec = rows16(q, q_bs, q_ts) && (D % 4) == 0;
+  a.ovec = rows16(o, o_bs, o_ts) && (D % 4) == 0;
+  a.rkey = key; a.thr = thr; a.keep_scale = scale_keep;
+  dim3 grid(Hh, B, (Tq + 63) / 64);
+  MRG_ATTN_DISPATCH_DROP(attn_fwd_kernel, grid, a);
+  return check_launch("attn_fwd_kernel<dropout>");
+}
+
+MRG_API int mrg_attention_bwd_dropout(int B, int Hh, int Tq, int Tk, int D,
+                                      const float* q, long q_bs, long q_ts, const float* k, long k_bs, long k_ts,
+                                      const float* v, long v_bs, long v_ts, const float* o, long o_bs, long o_ts,
+                                      const float* lse, const unsigned char* qpad, const unsigned char* kpad,
+                                      int causal, float scale, const float* dout, long do_bs, long do_ts,
+                                      float* dq, long dq_bs, long dq_ts, float* dk, long dk_bs, long dk_ts,
+                                      float* dv, long dv_bs, long dv_ts, float* workspace, unsigned int thr,
+                                      float scale_keep, const unsigned long long* key, hipStream_t stream) {
+  if (int e = attn_check(D, Tq, Tk, causal)) return e;
+  if (int e = drop_check(thr, scale_keep, key, B, Hh)) return e;
+  if (B == 0 || Tq == 0 || Tk == 0) return 0;
+  MRG_REQUIRE(rows16(q, q_bs, q_ts) && rows16(k, k_bs, k_ts) && rows16(v, v_bs, v_ts) &&
+              rows16(dout, do_bs, do_ts), "attention bwd: Q/K/V/dO rows must be 16-B aligned");
+  MRG_REQUIRE(workspace != nullptr, "attention bwd: workspace (B*heads*Tq floats) required");
+  AttnArgs a = attn_base(B, Hh, Tq, Tk, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse,
+                         qpad, kpad, causal, scale);
+  a.dout = dout; a.do_bs = do_bs; a.do_ts = do_ts; a.dlt = workspace;
+  a.dq = dq; a.dq_bs = dq_bs; a.dq_ts = dq_ts; a.dk = dk; a.dk_bs = dk_bs; a.dk_ts = dk_ts;
+  a.dv = dv; a.dv_bs = dv_bs; a.dv_ts = dv_ts;
+  a.qvec = 1;  // required above
+  a.ovec = rows16(o, o_bs, o_ts);
+  a.dkvvec = rows16(dk, dk_bs, dk_ts) && rows16(dv, dv_bs, dv_ts);
+  a.rkey = key; a.thr = thr; a.keep_scale = scale_keep;
+  dim3 gq(Hh, B, (Tq + 63) / 64);
+  MRG_ATTN_DISPATCH_DROP(attn_bwd_dq_kernel, gq, a);  // also writes delta = rowsum(dO * O) to the workspace
+  if (check_launch("attn_bwd_dq_kernel<dropout>")) return 1;
+  dim3 gk(Hh, B, (Tk + 63) / 64);
+  MRG_ATTN_DISPATCH_DROP(attn_bwd_dkv_kernel, gk, a);
+  return check_launch("attn_bwd_dkv_kernel<dropout>");
 }
 
 // Query-chunk forms (the block-level (block, time-chunk) wavefront, block_stack.py): the Tq query

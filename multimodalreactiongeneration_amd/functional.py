@@ -1740,6 +1740,120 @@ def gru_layer(x, w_ih, w_hh, b_ih, b_hh, h0=None, reverse=False):
     return _GRUFn.apply(bool(reverse), x, w_ih, w_hh, b_ih, b_hh, h0)
 
 
+# --- dropout RNG (csrc/rng.h, rng.py): a per-device {seed, draw} state in device memory.  An op that
+# drops takes one draw with a one-thread kernel (a graph node: a replayed step takes fresh draws) and
+# keeps the 16-byte key tensor for its backward.  All DDP ranks share the default seed unless the
+# caller seeds per rank (manual_seed(base + rank)).
+_RNG = {}
+
+
+def _i64(v: int) -> int:
+    v = int(v) & (2 ** 64 - 1)
+    return v - 2 ** 64 if v >= 2 ** 63 else v
+
+
+def _rng_device(device) -> torch.device:
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("the dropout RNG state lives on a HIP device")
+    return torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+
+
+def _rng_state(device) -> torch.Tensor:
+    dev = _rng_device(device)
+    if dev.index not in _RNG:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the dropout RNG state must exist before graph capture (run the step once, "
+                               "or call functional.manual_seed, first)")
+        from .rng import DEFAULT_SEED
+        _RNG[dev.index] = torch.tensor([_i64(DEFAULT_SEED), 0], dtype=torch.int64, device=dev)
+    return _RNG[dev.index]
+
+
+def manual_seed(seed: int, device=None) -> None:
+    """Reset the device's dropout RNG state to {seed, draw 0} (default seed: rng.DEFAULT_SEED)."""
+    set_rng_state(device, (seed, 0))
+
+
+def get_rng_state(device=None):
+    """(seed, draw) of the device's dropout RNG state as Python ints (synchronises)."""
+    seed, draw = _rng_state(device).tolist()
+    return seed & (2 ** 64 - 1), draw & (2 ** 64 - 1)
+
+
+def set_rng_state(device, state) -> None:
+    seed, draw = state
+    st = _rng_state(device)
+    st.copy_(torch.tensor([_i64(seed), _i64(draw)], dtype=torch.int64))
+
+
+def _drop_consts(p):
+    """(thr, scale_keep) of a dropout probability (ValueError outside [0, 1))."""
+    from .rng import threshold
+    return threshold(p), 1.0 / (1.0 - float(p))
+
+
+def _rng_draw(device) -> torch.Tensor:
+    """Take one draw: the op's key tensor {seed, draw} (int64 [2], device memory)."""
+    key = torch.empty(2, dtype=torch.int64, device=device)
+    _lib.check(_lib.load().mrg_rng_draw(_ptr(_rng_state(device)), _ptr(key), _stream()), "rng draw")
+    return key
+
+
+def dropout_keep_mask(key: torch.Tensor, n: int, p: float) -> torch.Tensor:
+    """uint8 [n]: the keep decisions functional.dropout makes with ``key`` (tests, debugging)."""
+    thr, _ = _drop_consts(p)
+    out = torch.empty(n, dtype=torch.uint8, device=key.device)
+    _lib.check(_lib.load().mrg_dropout_keep_mask(n, thr, _ptr(key), _ptr(out), _stream()), "dropout keep mask")
+    return out
+
+
+def attention_keep_mask(key: torch.Tensor, B: int, heads: int, Tq: int, Tk: int, p: float) -> torch.Tensor:
+    """uint8 [B, heads, Tq, Tk]: the keep decisions of an attention op that holds ``key``."""
+    thr, _ = _drop_consts(p)
+    out = torch.empty(B, heads, Tq, Tk, dtype=torch.uint8, device=key.device)
+    _lib.check(_lib.load().mrg_attention_keep_mask(B, heads, Tq, Tk, thr, _ptr(key), _ptr(out), _stream()),
+               "attention keep mask")
+    return out
+
+
+class _DropoutFn(Function):
+    """y = keep ? x / (1 - p) : 0 with one draw; the backward runs the same kernel on the gradient with
+    the saved key (no mask tensor is stored)."""
+
+    @staticmethod
+    def forward(ctx, x, p):
+        _lib.require_device(x)
+        thr, sk = _drop_consts(p)
+        xc = x.contiguous()
+        key = _rng_draw(xc.device)
+        y = torch.empty_like(xc)
+        _lib.check(_lib.load().mrg_dropout(xc.numel(), thr, sk, _ptr(key), _ptr(xc), _ptr(y), _stream()), "dropout")
+        ctx.save_for_backward(key)
+        ctx.consts = (thr, sk)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        _flush_touched()
+        (key,) = ctx.saved_tensors
+        thr, sk = ctx.consts
+        g = dy.contiguous()
+        dx = torch.empty_like(g)
+        _lib.check(_lib.load().mrg_dropout(g.numel(), thr, sk, _ptr(key), _ptr(g), _ptr(dx), _stream()), "dropout bwd")
+        return dx, None
+
+
+def dropout(x, p):
+    """Inverted dropout (training mode) on the library's counter-based RNG.  p = 0 returns x."""
+    thr, _ = _drop_consts(p)
+    if x.dtype != torch.float32:
+        raise ValueError("functional.dropout: float32 tensor required")
+    if float(p) == 0.0:
+        return x
+    return _DropoutFn.apply(x, float(p))
+
+
 def visible_pairs(Tq, Tk, causal):
     """(query, key) pairs the block-causal rule admits per (sample, head) (gen_attention_mask rules)."""
     if not causal:
@@ -1755,7 +1869,10 @@ class _MHAFn(Function):
     @staticmethod
     @_keeps_precision
     def forward(ctx, spec, q_in, kv_in, in_w, in_b, out_w, out_b, qpad, kpad, gamma=None, beta=None):
-        heads, causal, eps = spec  # eps not None: return LN(attn + q) (ResidualConnection(MHAMixer))
+        # eps not None: return LN(attn + q) (ResidualConnection(MHAMixer)); p > 0: dropout on the
+        # attention probabilities with one draw, the key saved for the backward
+        heads, causal, eps, *rest = spec
+        p = rest[0] if rest else 0.0
         _lib.require_device(q_in)
         dev = q_in.device
         B, Tq, E = q_in.shape
@@ -1771,11 +1888,20 @@ class _MHAFn(Function):
         lse = torch.empty(B, heads, Tq, device=dev, dtype=torch.float32)
         scale = 1.0 / math.sqrt(D)
         lib = _lib.load()
-        with _probe("attn_fwd", 4.0 * D * B * heads * visible_pairs(Tq, Tk, causal)):
-            rc = lib.mrg_attention_fwd(B, heads, Tq, Tk, D, _ptr(Q), Tq * E, E, _ptr(KV), Tk * 2 * E,
-                                         2 * E, _ptr(KV, E), Tk * 2 * E, 2 * E, _ptr(O), Tq * E, E,
-                                       _ptr(lse), _ptr(qpad), _ptr(kpad), int(causal), scale,
-                                       _stream())
+        drop = None
+        if p > 0.0:
+            thr, sk = _drop_consts(p)
+            drop = (thr, sk, _rng_draw(dev))
+            rc = lib.mrg_attention_fwd_dropout(B, heads, Tq, Tk, D, _ptr(Q), Tq * E, E, _ptr(KV), Tk * 2 * E,
+                                               2 * E, _ptr(KV, E), Tk * 2 * E, 2 * E, _ptr(O), Tq * E, E,
+                                               _ptr(lse), _ptr(qpad), _ptr(kpad), int(causal), scale,
+                                               thr, sk, _ptr(drop[2]), _stream())
+        else:
+            with _probe("attn_fwd", 4.0 * D * B * heads * visible_pairs(Tq, Tk, causal)):
+                rc = lib.mrg_attention_fwd(B, heads, Tq, Tk, D, _ptr(Q), Tq * E, E, _ptr(KV), Tk * 2 * E,
+                                           2 * E, _ptr(KV, E), Tk * 2 * E, 2 * E, _ptr(O), Tq * E, E,
+                                           _ptr(lse), _ptr(qpad), _ptr(kpad), int(causal), scale,
+                                           _stream())
         _lib.check(rc, "attention fwd")
         out = torch.empty(B, Tq, E, device=dev, dtype=torch.float32)
         _fwd_gemm(B * Tq, E, E, _ptr(O), E, out_w, _ptr(out), E, bias=_ptr(out_b), device=dev)
@@ -1792,6 +1918,7 @@ class _MHAFn(Function):
             extra = [out, gamma, beta, mean, rstd]
         ctx.save_for_backward(q2, kv2, Q, KV, O, lse, in_w, in_b, out_w, out_b, qpad, kpad, *extra)
         ctx.spec = (heads, causal, scale, eps is not None)
+        ctx.drop = drop
         return res
 
     @staticmethod
@@ -1819,12 +1946,20 @@ class _MHAFn(Function):
         dQ = torch.empty(B, Tq, E, device=dev, dtype=torch.float32)
         dKV = torch.empty(B, Tk, 2 * E, device=dev, dtype=torch.float32)
         ws = _ws(lib.mrg_attention_bwd_workspace_bytes(B, heads, Tq), dev)
-        with _probe("attn_bwd", 10.0 * D * B * heads * visible_pairs(Tq, Tk, causal)):
-            rc = lib.mrg_attention_bwd(
-            B, heads, Tq, Tk, D, _ptr(Q), Tq * E, E, _ptr(KV), Tk * 2 * E, 2 * E, _ptr(KV, E), Tk * 2 * E,
-            2 * E, _ptr(O), Tq * E, E, _ptr(lse), _ptr(qpad), _ptr(kpad), int(causal), scale,
-            _ptr(dO), Tq * E, E, _ptr(dQ), Tq * E, E, _ptr(dKV), Tk * 2 * E, 2 * E, _ptr(dKV, E),
-            Tk * 2 * E, 2 * E, _ptr(ws), _stream())
+        if ctx.drop is not None:
+            thr, sk, key = ctx.drop
+            rc = lib.mrg_attention_bwd_dropout(
+                B, heads, Tq, Tk, D, _ptr(Q), Tq * E, E, _ptr(KV), Tk * 2 * E, 2 * E, _ptr(KV, E), Tk * 2 * E,
+                2 * E, _ptr(O), Tq * E, E, _ptr(lse), _ptr(qpad), _ptr(kpad), int(causal), scale,
+                _ptr(dO), Tq * E, E, _ptr(dQ), Tq * E, E, _ptr(dKV), Tk * 2 * E, 2 * E, _ptr(dKV, E),
+                Tk * 2 * E, 2 * E, _ptr(ws), thr, sk, _ptr(key), _stream())
+        else:
+            with _probe("attn_bwd", 10.0 * D * B * heads * visible_pairs(Tq, Tk, causal)):
+                rc = lib.mrg_attention_bwd(
+                    B, heads, Tq, Tk, D, _ptr(Q), Tq * E, E, _ptr(KV), Tk * 2 * E, 2 * E, _ptr(KV, E), Tk * 2 * E,
+                    2 * E, _ptr(O), Tq * E, E, _ptr(lse), _ptr(qpad), _ptr(kpad), int(causal), scale,
+                    _ptr(dO), Tq * E, E, _ptr(dQ), Tq * E, E, _ptr(dKV), Tk * 2 * E, 2 * E, _ptr(dKV, E),
+                    Tk * 2 * E, 2 * E, _ptr(ws), _stream())
         _lib.check(rc, "attention bwd")
         gw, gb = _gbuf(in_w), _gbuf(in_b)
         _wgrad(_ptr(dQ), E, _ptr(q2), E, B * Tq, E, E, None if gw is None else gw[:E], dev,
@@ -1919,26 +2054,31 @@ def _one_key(q, kv):
 
 
 def mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal=False,
-        qpad=None, kpad=None):
-    """nn.MultiheadAttention(batch_first, kdim=vdim=E)(q, kv, kv) with the reference mask rules."""
+        qpad=None, kpad=None, dropout_p=0.0):
+    """nn.MultiheadAttention(batch_first, kdim=vdim=E)(q, kv, kv) with the reference mask rules.
+    dropout_p > 0: dropout on the attention probabilities (the module's training mode)."""
     if in_proj_weight.shape[0] != 3 * q.shape[-1]:
         raise ValueError("in_proj_weight must be [3E, E]")
-    if _one_key(q, kv):
+    p = float(dropout_p)
+    _drop_consts(p)
+    if p == 0.0 and _one_key(q, kv):   # with dropout the single probability 1 is still dropped: _MHAFn
         return _MHAOneKeyFn.apply(None, q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, qpad, kpad)
-    return _MHAFn.apply((heads, bool(causal), None), q, kv, in_proj_weight, in_proj_bias, out_weight,
+    return _MHAFn.apply((heads, bool(causal), None, p), q, kv, in_proj_weight, in_proj_bias, out_weight,
                         out_bias, qpad, kpad)
 
 
 def mha_residual_layernorm(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, gamma, beta,
-                           eps=1e-5, causal=False, qpad=None, kpad=None):
+                           eps=1e-5, causal=False, qpad=None, kpad=None, dropout_p=0.0):
     """LN(MHA(q, kv, kv) + q): ResidualConnection(MHAMixer) (mixer_block.py:567-603); the query
     projection's input-gradient GEMM takes the residual gradient in its epilogue."""
     if in_proj_weight.shape[0] != 3 * q.shape[-1]:
         raise ValueError("in_proj_weight must be [3E, E]")
-    if _one_key(q, kv):
+    p = float(dropout_p)
+    _drop_consts(p)
+    if p == 0.0 and _one_key(q, kv):
         return _MHAOneKeyFn.apply(float(eps), q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, qpad, kpad,
                                   gamma, beta)
-    return _MHAFn.apply((heads, bool(causal), float(eps)), q, kv, in_proj_weight, in_proj_bias, out_weight,
+    return _MHAFn.apply((heads, bool(causal), float(eps), p), q, kv, in_proj_weight, in_proj_bias, out_weight,
                         out_bias, qpad, kpad, gamma, beta)
 
 

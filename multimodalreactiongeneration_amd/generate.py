@@ -231,9 +231,24 @@ class GenPlan:
 _PLANS = {}
 
 
+def _dropout_active(module) -> bool:
+    """A submodule in training mode would drop: an MHA with p > 0, or a multi-layer LSTM / GRU with p > 0."""
+    from .model.layers import GRU, LSTM, MultiheadAttention
+    for m in module.modules():
+        if not (m.training and getattr(m, "dropout", 0.0)):
+            continue
+        if isinstance(m, MultiheadAttention) or (isinstance(m, (LSTM, GRU)) and m.num_layers > 1):
+            return True
+    return False
+
+
 def plan_for(model) -> Optional[GenPlan]:
-    """The model's GenPlan (cached per module identity and parameter storage), or None outside it."""
+    """The model's GenPlan (cached per module identity and parameter storage), or None outside it.
+    Eligibility is cached, so the one thing that changes with model.train() / eval() is re-checked on
+    every call: with an active dropout the frames take the module path, as the reference's would."""
     mf = model.metaformer
+    if _dropout_active(mf):
+        return None
     key = (id(mf), mf.feature_embedding[0].weight.data_ptr(), model.ratio)
     p = _PLANS.get(key)
     if p is None:

@@ -191,12 +191,15 @@ class LSTM(nn.Module):
         if pre is not None:
             if pre[0] is not x:
                 raise RuntimeError("LSTM: a paired result was left for a different input")
-            return pre[1]
-        if self.dropout and self.training and self.num_layers > 1:
-            _unsupported("LSTM inter-layer dropout")
+            return pre[1]   # one-layer LSTMs only (paired_lstm_layerd): no inter-layer dropout to skip
+        # nn.LSTM's inter-layer dropout: on the (concatenated) output of every layer but the last,
+        # one draw per layer in layer order
+        p_drop = self.dropout if (self.training and self.num_layers > 1) else 0.0
         D = 2 if self.bidirectional else 1
         hs, cs = [], []
         for layer in range(self.num_layers):
+            if layer and p_drop:
+                x = Fn.dropout(x, p_drop)
             if D == 1:
                 h0 = None if hx is None else hx[0][layer]
                 c0 = None if hx is None else hx[1][layer]
@@ -247,11 +250,12 @@ class GRU(nn.Module):
                 getattr(self, f"bias_ih_{sfx}"), getattr(self, f"bias_hh_{sfx}"))
 
     def forward(self, x, hx=None):
-        if self.dropout and self.training and self.num_layers > 1:
-            _unsupported("GRU inter-layer dropout")
+        p_drop = self.dropout if (self.training and self.num_layers > 1) else 0.0   # as nn.GRU (see LSTM)
         D = 2 if self.bidirectional else 1
         hs = []
         for layer in range(self.num_layers):
+            if layer and p_drop:
+                x = Fn.dropout(x, p_drop)
             ys = []
             for d in range(D):
                 h0 = None if hx is None else hx[layer * D + d]
@@ -289,8 +293,6 @@ class MultiheadAttention(nn.Module):
             _unsupported("MHA with distinct key and value tensors")
         if key_padding_mask is not None or need_weights:
             _unsupported("MHA key_padding_mask / need_weights")
-        if self.dropout and self.training:
-            _unsupported("attention dropout")
         if not self.batch_first:
             query, key = query.transpose(0, 1), key.transpose(0, 1)
         causal, qpad, kpad = False, None, None
@@ -299,7 +301,8 @@ class MultiheadAttention(nn.Module):
                 _unsupported("dense attn_mask (use masks.gen_attention_mask)")
             causal, qpad, kpad = True, attn_mask.main_pad, attn_mask.other_pad
         out = Fn.mha(query, key, self.in_proj_weight, self.in_proj_bias, self.out_proj.weight,
-                     self.out_proj.bias, self.num_heads, causal, qpad, kpad)
+                     self.out_proj.bias, self.num_heads, causal, qpad, kpad,
+                     dropout_p=self.dropout if self.training else 0.0)
         if not self.batch_first:
             out = out.transpose(0, 1)
         return out, None

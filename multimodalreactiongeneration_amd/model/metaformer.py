@@ -387,6 +387,12 @@ class MultiModalMetaformer(nn.Module):
                     if not (isinstance(m, LSTMMixerBlock) and isinstance(m.mixer, ResidualConnection)
                             and m.mixer.layer_norm is not None):
                         return False
+                    # the fused LN(LSTM(x) + x) takes layer 0's parameters only: a stacked or
+                    # bidirectional LSTM (num_internal_layer > 1, with its inter-layer dropout) runs
+                    # through layers.LSTM on the module path
+                    lstm = m.mixer.module.mixer
+                    if lstm.num_layers != 1 or lstm.bidirectional:
+                        return False
         return True
 
     def forward(self, main_modal, other_modals, hx=None, main_modal_others=None, other_modals_others=None,

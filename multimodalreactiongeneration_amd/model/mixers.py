@@ -96,7 +96,7 @@ class MHAMixer(Mixer):
         if len(self.mixer) != 1 or k is not v or self.mixer[0].nonlinearity is not None:
             return None
         mha = self.mixer[0].mha
-        if not mha.batch_first or (mha.dropout and mha.training):
+        if not mha.batch_first:
             return None
         if attn_mask is not None and not isinstance(attn_mask, BlockCausalMask):
             return None
@@ -105,7 +105,7 @@ class MHAMixer(Mixer):
             causal, qpad, kpad = True, attn_mask.main_pad, attn_mask.other_pad
         return Fn.mha_residual_layernorm(q, k, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
                                          mha.out_proj.bias, mha.num_heads, ln.weight, ln.bias, ln.eps,
-                                         causal, qpad, kpad)
+                                         causal, qpad, kpad, dropout_p=mha.dropout if mha.training else 0.0)
 
     def forward(self, q, k, v, attn_mask=None):
         if len(self.mixer) > 1:
