@@ -542,6 +542,29 @@ int mrg_broadcast_loss_bwd(int B, int T, int F, const float* y, long y_bstride, 
                            float beta, int t_start, float dscale, const float* grad_out, float* dy,
                            float* workspace, hipStream_t stream);
 
+/* ---------------------------------------------------------------- per-target metrics
+ * MultiTargetMetrics (mr_gen/utils/metrics/multi_modal_metrics.py:6-56): one mean squared error per
+ * column range [starts[k], ends[k]) of the last axis (ends[k] = -1: F; 1 <= K <= 8; ranges may overlap;
+ * starts / ends are host arrays, copied into the launch).  Per element the term is the mse term of
+ * the loss above: d = (y m) s - (t m) s with the padding mask m and the feature scaler s of
+ * mrg_masked_loss_fwd (mask_padding = 0, dscale = 1: a plain update(preds, target)), or, in the
+ * broadcast form, the [Tm, B, T, F] collapse of mrg_broadcast_loss_fwd (t_start, dscale).
+ * state: double [K][2] in device memory, advanced by the kernel: state[k][0] += sum of the terms,
+ * state[k][1] += count_k = B * T * (end_k - start_k) (times Tm in the broadcast form; padded
+ * positions count).  batch_out [K] = this call's sum / count_k.  Two launches (the broadcast form
+ * counts the non-padded motion_s frames first), no atomics: identical calls leave bitwise-equal
+ * state.  workspace: mrg_target_metrics_workspace_bytes, for either form.                      */
+size_t mrg_target_metrics_workspace_bytes(int B, int T, int F);
+int mrg_target_metrics_update(int B, int T, int F, const float* y, long y_bstride, const float* target,
+                              int mask_padding, int delta_start, float dscale, int K, const int* starts,
+                              const int* ends, double* state, float* batch_out, float* workspace,
+                              hipStream_t stream);
+int mrg_target_metrics_update_broadcast(int B, int T, int F, const float* y, long y_bstride,
+                                        const float* target, const float* ms, long ms_bs, long ms_ts,
+                                        int Tm, int t_start, float dscale, int K, const int* starts,
+                                        const int* ends, double* state, float* batch_out,
+                                        float* workspace, hipStream_t stream);
+
 /* ---------------------------------------------------------------- AdamW
  * torch.optim.AdamW step over flat buffers (configure_optimizers,
  * lstmformer.py:327-333).  step_lr = device float[2] {steps done, lr}.

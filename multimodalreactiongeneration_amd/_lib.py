@@ -156,6 +156,11 @@ SIGNATURES = {
                                        c_float, c_float, c_int, c_float, P, P, P]),
     "mrg_broadcast_loss_bwd": (c_int, [c_int, c_int, c_int, P, c_long, P, P, c_long, c_long, c_int, c_int,
                                        c_float, c_float, c_int, c_float, P, P, P, P]),
+    "mrg_target_metrics_workspace_bytes": (c_size, [c_int, c_int, c_int]),
+    "mrg_target_metrics_update": (c_int, [c_int, c_int, c_int, P, c_long, P, c_int, c_int, c_float, c_int, PI, PI,
+                                          P, P, P, P]),
+    "mrg_target_metrics_update_broadcast": (c_int, [c_int, c_int, c_int, P, c_long, P, P, c_long, c_long, c_int,
+                                                    c_int, c_float, c_int, PI, PI, P, P, P, P]),
     "mrg_ssd_gate_cell_fwd": (c_int, [c_int, c_int, c_int, P, P, P, P, P, c_float, P, P, P, P, P, P, P, P, P, P]),
     "mrg_ssd_gate_cell_fwd_dbg": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, P, c_float, P, P, P, P, P, P, P,
                                           P, P, P]),

@@ -2211,3 +2211,71 @@ def broadcast_masked_loss(pred, target, motion_self, loss_type="huber", delta=1.
     spec = (_LOSS_TYPES[loss_type], float(delta), float(beta), int(t_start),
             float(math.sqrt(delta_loss_scale)) if scaler else 1.0)
     return _BcastLossFn.apply(pred, target, motion_self, spec)
+
+
+# ------------------------------------------------------------------ per-target metrics
+# MultiTargetMetrics' updates (metrics.py): not autograd ops.  The inputs are detached, nothing is allocated
+# but _ws workspace, and the accumulators are advanced by the kernels, so the calls may sit inside a captured
+# step.  state: float64 [K, 2] on the device ({sum, count} per range); batch_out: float32 [K].
+def _metric_ranges(ranges):
+    K = len(ranges)
+    if not 1 <= K <= 8:
+        raise ValueError(f"target metrics: {K} ranges (1..8 supported)")
+    arr = ctypes.c_int * K
+    return K, arr(*[int(s) for s, _ in ranges]), arr(*[int(e) for _, e in ranges])
+
+
+def _metric_buffers(y, state, batch_out, K):
+    _lib.require_device(y)
+    if not (state.is_cuda and state.dtype == torch.float64 and state.is_contiguous() and state.numel() == 2 * K
+            and batch_out.is_cuda and batch_out.dtype == torch.float32 and batch_out.is_contiguous()
+            and batch_out.numel() == K and state.device == y.device == batch_out.device):
+        raise RuntimeError("target metrics: state must be float64 [K, 2] and batch_out float32 [K] on y's device")
+
+
+def target_metrics_update(y, target, ranges, state, batch_out, lead=0, mask_padding=False, delta_order=0,
+                          delta_loss_scale=1.0):
+    """state += the squared-error sums / counts of y[:, lead:] vs target over each (start, end) of ranges,
+    with masked_loss's padding mask and delta scaler; batch_out = this call's means."""
+    y, target = y.detach(), target.detach()
+    K, starts, ends = _metric_ranges(ranges)
+    _metric_buffers(y, state, batch_out, K)
+    if y.dtype != torch.float32 or target.dtype != torch.float32 or target.device != y.device:
+        raise RuntimeError("target metrics: float32 tensors on one device required")
+    y, target = y.contiguous(), target.contiguous()
+    B, Ttot, F = y.shape
+    T = target.shape[1]
+    if Ttot - lead != T or target.shape[0] != B or target.shape[2] != F:
+        raise RuntimeError(f"target metrics shape mismatch: y{tuple(y.shape)}[:, {lead}:] vs "
+                           f"target{tuple(target.shape)}")
+    lib = _lib.load()
+    ws = _ws(lib.mrg_target_metrics_workspace_bytes(B, T, F), y.device)
+    _lib.check(lib.mrg_target_metrics_update(B, T, F, _ptr(y, lead * F), Ttot * F, _ptr(target), int(mask_padding),
+                                             int(F // (delta_order + 1)), float(math.sqrt(delta_loss_scale)), K,
+                                             starts, ends, _ptr(state), _ptr(batch_out), _ptr(ws), _stream()),
+               "target metrics update")
+    return batch_out
+
+
+def target_metrics_update_broadcast(pred, target, motion_self, ranges, state, batch_out, scaler=True, delta_order=0,
+                                    delta_loss_scale=1.0):
+    """The same over the reference's broadcast [Tm, B, T, F] target (broadcast_masked_loss),
+    collapsed analytically; range k counts Tm * B * T * (end_k - start_k) elements."""
+    pred, target, ms = pred.detach(), target.detach(), motion_self.detach()
+    K, starts, ends = _metric_ranges(ranges)
+    _metric_buffers(pred, state, batch_out, K)
+    if any(t.dtype != torch.float32 or t.device != pred.device for t in (pred, target, ms)):
+        raise RuntimeError("target metrics: float32 tensors on one device required")
+    pred, target = pred.contiguous(), target.contiguous()
+    B, T, F = pred.shape
+    if tuple(target.shape) != (B, T, F) or ms.dim() != 3 or ms.shape[0] != B or ms.shape[2] != F or ms.stride(2) != 1:
+        raise RuntimeError(f"broadcast metrics shapes: y{tuple(pred.shape)} target{tuple(target.shape)} "
+                           f"motion_self{tuple(ms.shape)}")
+    t_start = T // (delta_order + 1) if scaler else T + 1
+    lib = _lib.load()
+    ws = _ws(lib.mrg_target_metrics_workspace_bytes(B, T, F), pred.device)
+    _lib.check(lib.mrg_target_metrics_update_broadcast(
+        B, T, F, _ptr(pred), T * F, _ptr(target), _ptr(ms), ms.stride(0), ms.stride(1), ms.shape[1], int(t_start),
+        float(math.sqrt(delta_loss_scale)) if scaler else 1.0, K, starts, ends, _ptr(state), _ptr(batch_out),
+        _ptr(ws), _stream()), "target metrics update (broadcast)")
+    return batch_out

@@ -11,7 +11,9 @@ or a plain dict).  ``forward`` / ``training_step`` / ``validation_step`` /
 signatures and return conventions.  pytorch_lightning is not a dependency:
 ``LightningSurface`` provides ``log`` / ``log_dict`` / ``current_epoch`` /
 ``device`` so a Lightning ``Trainer`` or a plain loop can drive the models.
-torchmetrics logging is out of scope (no effect on loss or grads).
+The per-target MSE metrics (``train_metrics`` / ``valid_metrics`` / ``genrt_metrics``, metrics.py) are
+updated by every step on the device; they read the step's tensors only, so losses and gradients are
+the same with ``metrics_enabled`` on or off.
 
 Precision switch: ``model.precision`` ("32" default; "bf16" / "bf16-mixed" as Lightning's
 Trainer(precision=...) names it, or the config key ``precision``) selects the arithmetic of every
@@ -32,6 +34,7 @@ from torch import nn
 
 from .. import functional as Fn
 from ..configs import as_attr
+from ..metrics import MultiTargetMetrics
 from ..optim import FusedAdamW
 from .layers import (Linear, LSTMSampler, LSTMLayerd, MultimodalAttention, ResidualConnection, paired_lstm_layerd,
                      run_sequential_ffn)
@@ -56,6 +59,9 @@ class LightningSurface(nn.Module):
 
     current_epoch = 0
     precision = "32"
+    # False skips every metric update; train_step_metrics = False skips training_step's alone
+    metrics_enabled = True
+    train_step_metrics = True
 
     def set_precision(self, precision):
         """'32' (fp32 arithmetic) or 'bf16' / 'bf16-mixed' (bf16 GEMM operands, fp32 accumulation)."""
@@ -73,6 +79,17 @@ class LightningSurface(nn.Module):
     @property
     def device(self):
         return next(self.parameters()).device
+
+    def _make_metrics(self, cfg, genrt=True):
+        """train_ / valid_ (/ genrt_) MultiTargetMetrics over gen_target_dict (lstmformer.py:217-229)."""
+        self.target_dict = gen_target_dict(cfg)
+        self.train_metrics = MultiTargetMetrics(self.target_dict, prefix="train_")
+        self.valid_metrics = MultiTargetMetrics(self.target_dict, prefix="valid_")
+        if genrt:
+            self.genrt_metrics = MultiTargetMetrics(self.target_dict, prefix="genrt_")
+
+    def _train_metrics_on(self):
+        return self.metrics_enabled and self.train_step_metrics
 
     def _loss_spec(self, cfg):
         return dict(loss_type=cfg.loss_type, delta=cfg.get("huber_delta", 1.0),
@@ -217,7 +234,7 @@ class Metaformer(LightningSurface):
         self.lr_scheduler = None
         self.delta_loss_scale = model.get("delta_loss_scale", 1.0)
         self.delta_order = metrics.delta_order
-        self.target_dict = gen_target_dict(metrics)
+        self._make_metrics(metrics)
 
     @_in_precision
     def forward(self, acoustic_partner, motion_partner, motion_self, leading_acoustic_partner,
@@ -255,10 +272,12 @@ class Metaformer(LightningSurface):
         if self.use_scheduled_sampling:
             self.log("scheduled_sampling_rate", self.current_epoch / self.max_epochs, logger=True)
             pred = self._generate(batch, use_scheduled_sampling=True, sampling_mask=sampling_mask)
+            target, ms = batch[-1][0].to(pred.device), batch[2][0].to(pred.device)
             # the reference's loss over the [T, B, T, F] broadcast target (Q9, lstmformer.py:372-380)
-            loss = Fn.broadcast_masked_loss(pred, batch[-1][0].to(pred.device), batch[2][0].to(pred.device),
-                                            self.model.loss_type, self.huber_delta, self.smoothl1_beta, True,
-                                            self.delta_order, self.delta_loss_scale)
+            loss = Fn.broadcast_masked_loss(pred, target, ms, self.model.loss_type, self.huber_delta,
+                                            self.smoothl1_beta, True, self.delta_order, self.delta_loss_scale)
+            if self._train_metrics_on():
+                self.train_metrics.update_broadcast(pred, target, ms, True, self.delta_order, self.delta_loss_scale)
         else:
             lead = batch[4][0].shape[1]
             target = batch[-1][0]
@@ -266,16 +285,23 @@ class Metaformer(LightningSurface):
             batch[2] = (Fn.zero_padding(ms, PADDING_VALUE), batch[2][1])
             y, _ = self.forward(*batch[:-1])
             loss = self._masked_loss(y, target, lead)
+            if self._train_metrics_on():
+                self.train_metrics.update_masked(y, target.to(y.device), lead, True, self.delta_order,
+                                                 self.delta_loss_scale)
         self.log("train_loss", loss, prog_bar=True, logger=True)
+        self.log_dict(self.train_metrics, logger=True, on_epoch=True, on_step=True)
         return {"loss": loss}
 
     @_in_precision
     def validation_step(self, batch: List, *args):
         lead = batch[4][0].shape[1]
         y, _ = self.forward(*batch[:-1])
-        loss = Fn.masked_loss(y, batch[-1][0].to(y.device), lead, self.model.loss_type, self.huber_delta,
-                              self.smoothl1_beta, True)
+        target = batch[-1][0].to(y.device)
+        loss = Fn.masked_loss(y, target, lead, self.model.loss_type, self.huber_delta, self.smoothl1_beta, True)
         self.log("val_loss", loss, prog_bar=True, logger=True)
+        if self.metrics_enabled:
+            self.valid_metrics.update_masked(y, target, lead, True)
+        self.log_dict(self.valid_metrics, logger=True, on_epoch=True, on_step=True)
         gen_loss = self.generation_step(batch)["loss"]
         return {"loss": loss, "gen_loss": gen_loss}
 
@@ -284,9 +310,13 @@ class Metaformer(LightningSurface):
         """genrt_loss (lstmformer.py:410-424): teacher-forced generation, loss over the broadcast
         [T, B, T, F] target of prediction (Q9), no scaler."""
         pred = self._generate(batch, sampling_mask=sampling_mask)
-        loss = Fn.broadcast_masked_loss(pred, batch[-1][0].to(pred.device), batch[2][0].to(pred.device),
-                                        self.model.loss_type, self.huber_delta, self.smoothl1_beta, scaler=False)
+        target, ms = batch[-1][0].to(pred.device), batch[2][0].to(pred.device)
+        loss = Fn.broadcast_masked_loss(pred, target, ms, self.model.loss_type, self.huber_delta,
+                                        self.smoothl1_beta, scaler=False)
         self.log("genrt_loss", loss, prog_bar=False, logger=True)
+        if self.metrics_enabled:
+            self.genrt_metrics.update_broadcast(pred, target, ms, scaler=False)
+        self.log_dict(self.genrt_metrics, logger=True, on_epoch=True, on_step=True)
         return {"loss": loss}
 
     # ---------------- autoregressive generation (lstmformer.py:426-559)
@@ -387,7 +417,7 @@ class LSTMwithSample(LightningSurface):
         self.delta_loss_scale = model.get("delta_loss_scale", 1.0)
         self.all_static = model.get("all_static", False)
         self.delta_order = metrics.delta_order
-        self.target_dict = gen_target_dict(metrics)
+        self._make_metrics(metrics)
 
     @_in_precision
     def forward(self, acoustic_partner, motion_partner, motion_self, leading_acoustic_partner,
@@ -424,19 +454,30 @@ class LSTMwithSample(LightningSurface):
         else:
             y, (lead, _, _), _ = self.forward(*batch[:-1])
             target = batch[-1][0]
-        loss = Fn.masked_loss(y, target.to(y.device), lead, self.model.loss_type, self.huber_delta,
+        target = target.to(y.device)
+        loss = Fn.masked_loss(y, target, lead, self.model.loss_type, self.huber_delta,
                               self.smoothl1_beta, True, self.delta_order, self.delta_loss_scale)
         self.log("train_loss", loss, prog_bar=True, logger=True)
+        if self._train_metrics_on():
+            self.train_metrics.update_masked(y, target, lead, True, self.delta_order, self.delta_loss_scale)
+        self.log_dict(self.train_metrics, logger=True, on_epoch=True, on_step=True)
         return {"loss": loss}
 
     @_in_precision
     def validation_step(self, batch: List, *args):
         y, (lead, _, _), _ = self.forward(*batch[:-1])
-        loss = Fn.masked_loss(y, batch[-1][0].to(y.device), lead, self.model.loss_type, self.huber_delta,
-                              self.smoothl1_beta, True)
+        target = batch[-1][0].to(y.device)
+        loss = Fn.masked_loss(y, target, lead, self.model.loss_type, self.huber_delta, self.smoothl1_beta, True)
         self.log("val_loss", loss, prog_bar=True, logger=True)
+        if self.metrics_enabled:
+            self.valid_metrics.update_masked(y, target, lead, True)
+        self.log_dict(self.valid_metrics, logger=True, on_epoch=True, on_step=True)
+        # generation phase (generation_step, lstm_with_sample.py:323-337)
         pred, target = self.prediction(batch)
         gen_loss = Fn.masked_loss(pred, target, 0, self.model.loss_type, self.huber_delta, self.smoothl1_beta, True)
+        if self.metrics_enabled:
+            self.genrt_metrics.update_masked(pred, target, 0, True)
+        self.log_dict(self.genrt_metrics, logger=True, on_epoch=True, on_step=True)
         return {"loss": loss, "gen_loss": gen_loss}
 
     @_in_precision
@@ -616,6 +657,7 @@ class SimpleLSTM(LightningSurface):
         self.delta_loss_scale = cfg.get("delta_loss_scale", 1.0)
         self.all_static = cfg.get("all_static", False)
         self.delta_order = metrics.delta_order
+        self._make_metrics(metrics, genrt=False)
 
     # MI355X schedule: the acoustic and motion encoders' block-i recurrences share one launch
     # (layers.paired_lstm_layerd); MRG_PAIR_ENCODERS=0 runs the encoders one after the other
@@ -654,9 +696,13 @@ class SimpleLSTM(LightningSurface):
         y = self.forward(a.to(dev), m.to(dev))
         if self.all_static:
             y = self.split_and_form(m.to(dev), y)
-        loss = Fn.masked_loss(y, target.to(dev), 0, "mse", mask_padding=False,
+        target = target.to(dev)
+        loss = Fn.masked_loss(y, target, 0, "mse", mask_padding=False,
                               delta_order=self.delta_order, delta_loss_scale=self.delta_loss_scale)
         self.log("train_loss", loss, prog_bar=True, logger=True)
+        if self._train_metrics_on():
+            self.train_metrics.update_masked(y, target, 0, False, self.delta_order, self.delta_loss_scale)
+        self.log_dict(self.train_metrics, logger=True, on_epoch=True, on_step=True)
         return {"loss": loss}
 
     @_in_precision
@@ -666,8 +712,12 @@ class SimpleLSTM(LightningSurface):
         y = self.forward(a.to(dev), m.to(dev))
         if self.all_static:
             y = self.split_and_form(m.to(dev), y)
-        loss = Fn.masked_loss(y, target.to(dev), 0, "mse", mask_padding=False)
+        target = target.to(dev)
+        loss = Fn.masked_loss(y, target, 0, "mse", mask_padding=False)
         self.log("val_loss", loss, prog_bar=True, logger=True)
+        if self.metrics_enabled:
+            self.valid_metrics.update_masked(y, target, 0, False)
+        self.log_dict(self.valid_metrics, logger=True, on_epoch=True, on_step=True)
         return {"loss": loss}
 
 
