@@ -194,7 +194,7 @@ class GradReducer:
         self._task = None
 
     def _launch(self, b):
-        from . import functional as Fn
+        from .wgrad_streams import side_stream
         s, e = self.buckets[b]
         self.launched[b] = True
         self.order.append(b)
@@ -203,7 +203,7 @@ class GradReducer:
         if self.stream is not None:
             cur = torch.cuda.current_stream(dev)
             self.stream.wait_stream(cur)
-            side = Fn._SIDE.get(dev.index or 0)
+            side = side_stream(dev)   # the recurrence stream is never used while a listener is set
             if side is not None:
                 self.stream.wait_stream(side)
             with torch.cuda.stream(self.stream):

@@ -40,6 +40,7 @@ from torch.autograd import Function
 from . import _lib
 from . import functional as Fn
 from .functional import _ptr, _stream, gemm, _dx_gemm, _wt_note, _gbuf, _on_side
+from .wgrad_streams import beside_recurrence
 
 # time steps per chunk (the diagonal width); MRG_STACK_CHUNK overrides.  100 since the deferred weight
 # gradients run beside the backward recurrences (longer recurrences leave them more room): A/B on one
@@ -150,16 +151,15 @@ def _launch_bwd(lib, items, B, Tc, H, dev, pool=None):
         lay += [4 * H, B * 4 * H, H, B * H, H, 4 * H, B * 4 * H, 0]
         rev.append(0)
     A = lambda ct, v: (ct * n)(*v)  # noqa: E731
-    # deferred weight gradients (functional._DEFER) run beside this recurrence, as in _LSTMFn.backward
-    cap, mark = Fn.fork_beside_recurrence(dev)
-    lib.mrg_lstm_set_blocks_per_cu(cap)
-    with Fn._probe("lstm_bwd", 8.0 * H * H * B * Tc * n):
-        rc = lib.mrg_lstm_bwd(n, B, Tc, H, A(VP, whh), A(VP, gates), A(VP, cs), A(VP, c0), A(VP, dy),
-                              A(CL, dybs), A(CL, dyts), A(VP, dhT), A(VP, dcT), A(VP, dG), A(VP, dh0), A(VP, dc0),
-                              A(CI, rev), A(VP, [_p(xb[i]) for i in range(n)]), (CL * (8 * n))(*lay),
-                              _ptr(Fn._err_flag(dev)), _lib.cu_count(dev.index or 0), 0, _stream())
-    _lib.check(rc, "lstm bwd (encoder stack)")
-    Fn.flush_beside_recurrence(dev, mark)
+    # deferred weight gradients (wgrad_streams._DEFER) run beside this recurrence, as in _LSTMFn.backward
+    with beside_recurrence(dev) as cap:
+        lib.mrg_lstm_set_blocks_per_cu(cap)
+        with Fn._probe("lstm_bwd", 8.0 * H * H * B * Tc * n):
+            rc = lib.mrg_lstm_bwd(n, B, Tc, H, A(VP, whh), A(VP, gates), A(VP, cs), A(VP, c0), A(VP, dy),
+                                  A(CL, dybs), A(CL, dyts), A(VP, dhT), A(VP, dcT), A(VP, dG), A(VP, dh0), A(VP, dc0),
+                                  A(CI, rev), A(VP, [_p(xb[i]) for i in range(n)]), (CL * (8 * n))(*lay),
+                                  _ptr(Fn._err_flag(dev)), _lib.cu_count(dev.index or 0), 0, _stream())
+        _lib.check(rc, "lstm bwd (encoder stack)")
 
 
 _BMAX = 16   # problems per batched GEMM / LayerNorm launch (mrg_gemm_x6g_batched, mrg_residual_layernorm_*_batched)
@@ -460,7 +460,7 @@ class _EncoderStackFn(Function):
     def _weight_grads(lib, ch, st, gr, l, B, H, dev, t0, t1, bo):
         """Layer l's parameter gradients over time steps [t0, t1) (one chunk, or the whole sequence once
         its last chunk is done), accumulated into the gradient buffers and issued as ONE fork onto the
-        weight-gradient side stream (functional._side); bo = the chunk's first LayerNorm partial block.
+        weight-gradient side stream (wgrad_streams.side); bo = the chunk's first LayerNorm partial block.
         Rows are time-major, so a chunk is one contiguous row range."""
         T = ch.T
         r0, rows = t0 * B, (t1 - t0) * B

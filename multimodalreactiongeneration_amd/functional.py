@@ -28,6 +28,10 @@ import torch
 from torch.autograd import Function
 
 from . import _lib
+# the weight-gradient stream scheduler; the names stay reachable here (bench.py, decode.py, tests, tools)
+from .wgrad_streams import (_LAST_FORK, _SIDE_MIN_ROWS, _conflicts, _fork, _writes, allow_defer,  # noqa: F401
+                            beside_recurrence, hold_scratch, on_side, reset_fork_point, set_wgrad_defer,
+                            set_wgrad_stream, side as _side)
 
 F32 = 4
 _ERR = {}
@@ -127,28 +131,8 @@ def _stream():
 
 def _ws(nbytes: int, device) -> torch.Tensor:
     t = torch.empty(max(1, (int(nbytes) + 3) // 4), dtype=torch.float32, device=device)
-    _hold_if_side(t)
+    hold_scratch(t)
     return t
-
-
-# MRG_SIDE_HOLD=0 turns the hold off (diagnostic only: tests/test_gpu_capture.py)
-_HOLD_SIDE_SCRATCH = [os.environ.get("MRG_SIDE_HOLD", "1") == "1"]
-
-
-def _hold_if_side(t: torch.Tensor):
-    """A scratch tensor allocated on the weight-gradient side stream stays referenced until the
-    backward's join (see _ensure_join).  Freed earlier, its block could go to an allocation on the
-    main stream while the side-stream kernel that uses it has not run yet: inside a HIP-graph capture
-    the private pool does not keep the two streams' blocks apart (measured: the encoder stack's
-    replayed gradients were corrupted by split-K slabs reused as main-stream temporaries)."""
-    if not (_SIDE and _HOLD_SIDE_SCRATCH[0]):
-        return
-    dev = t.device.index or 0
-    s = _SIDE.get(dev)
-    cur = torch.cuda.current_stream(t.device)
-    if (s is not None and (cur == s or cur == _REC.get(dev)) and dev in _JOIN_PENDING
-            and torch.cuda.is_current_stream_capturing()):
-        _SIDE_HOLD.setdefault(dev, []).append(t)
 
 
 def _counters(device) -> torch.Tensor:
@@ -191,6 +175,7 @@ def set_grad_listener(listener):
     (at most one autograd Function late); listener.end_of_backward() once per backward pass."""
     _GRAD_LISTENER[0] = listener
     _TOUCHED.clear()
+    allow_defer(listener is None)   # each write is issued when it is reported
 
 
 def _flush_touched():
@@ -287,7 +272,7 @@ def act_splits(M, N, K):
 
 
 # Workgroups a weight-gradient product aims at.  256 (half the split-K slices of round 2's 512): most
-# products run beside a recurrence with the grid capped at one block per CU (_DEFER), where fewer
+# products run beside a recurrence with the grid capped at one block per CU (wgrad_streams._DEFER), where fewer
 # slices measured faster (tools/tools_wgrad_sweep.py, capped grid: LSTM dW 1024 x 256 102 -> 98 us at
 # 16 instead of 32 slices, 256 x 256 41 -> 36 us at 64 instead of 128, 512 x 256 62 -> 55 us at 32
 # instead of 64) and the slab reduce reads half the slabs: 22.93 -> 22.48 ms/step on one box (128:
@@ -320,311 +305,10 @@ def colsum(rows, N, X, ld, out, *, out2=None, beta=1.0, ld_hi=0, rdiv=0, device=
                "colsum")
 
 
-# --- weight gradients on a side stream
-# Parameter gradients are consumed only by the optimizer / all-reduce, so the weight-gradient
-# GEMMs (dW = dY^T X, fused bias sums) leave the backward's critical path: they run on one side
-# stream per device, forked from the current stream when their operands are ready and joined back
-# at the end of the backward pass (an autograd final callback), so `loss.backward()` returns with
-# every gradient ordered before anything the caller issues next (graph capture included).  Their
-# operands are record_stream'ed so the caching allocator does not recycle them early.  Products
-# over fewer than _SIDE_MIN_ROWS rows (the T = 1 decode steps of the autoregressive loops, where
-# a fork/join per frame costs more than it hides: C3 scheduled sampling 80 -> 130 ms measured)
-# stay on the current stream; if the side stream already has work in this backward pass, the
-# current stream first waits for it, so the writes into any one gradient buffer stay in order.
-# MRG_WGRAD_STREAM=0 (or set_wgrad_stream(False)) issues everything on the current stream.
-_WGRAD_SIDE = [os.environ.get("MRG_WGRAD_STREAM", "1") != "0"]
-_SIDE_MIN_ROWS = 2048
-_SIDE = {}
-_SIDE_HOLD = {}   # device -> side-stream scratch tensors kept alive until the join (_hold_if_side)
-# device -> autograd graph-task id whose final callback will join the side stream back.  Keyed by
-# the task (torch._C._current_graph_task_id), not a bare flag: a backward that raised after a fork
-# never ran its callback, and a stale flag would make every later backward skip the join.
-_JOIN_PENDING = {}
-
-
-def set_wgrad_stream(on: bool) -> bool:
-    """Enable / disable side-stream weight gradients; returns the previous setting."""
-    prev = _WGRAD_SIDE[0]
-    _WGRAD_SIDE[0] = bool(on)
-    return prev
-
-
-# Deferred weight gradients (on by default, MRG_WGRAD_DEFER=0 turns it off; neutral in round 2, -0.34 ms/step
-# with round 3's encoder wavefront, whose MFMA recurrences leave room on every CU): a side-stream product is not issued
-# when its operands are ready but queued until the backward reaches its next persistent recurrence
-# (_LSTMFn.backward marks the current stream right before mrg_lstm_bwd and issues the queue right
-# after it, ordered after the mark only: fork_beside_recurrence / flush_beside_recurrence), on the
-# side stream with the GEMM grids capped at one block per CU while the recurrence runs at one
-# workgroup per CU (mrg_lstm_set_blocks_per_cu): the latency-bound recurrence leaves most of each
-# CU idle, and the dW products fill it instead of running beside the dX chain's GEMMs (which
-# already fill the GPU).  The end-of-backward join issues whatever is still queued.  Queue order is
-# side-stream order, so the writes into each gradient buffer keep their order; a write issued on the
-# current stream (fewer than _SIDE_MIN_ROWS rows) first flushes the queue.  Not used while a
-# gradient-ready listener (DDP bucket overlap) needs each write issued when it is reported.
-_DEFER = [os.environ.get("MRG_WGRAD_DEFER", "1") == "1"]
-_PENDING = {}
-# The queue flushed beside the recurrences runs on a stream of its own (_REC), the rest of the side
-# work (the end-of-backward flush: the products of the layers below the last recurrence) on _SIDE, so
-# that flush starts when its operands are ready instead of behind the recurrence stream's backlog
-# (in-graph wall-clock stamps, tools/side_timing.py: that backlog outlasts the main stream by ~1.7 ms;
-# headline 20.55 -> 20.23 ms, A/B on one box).  Writes into one gradient buffer stay ordered: every
-# queued item names the buffers it writes (_on_side(writes=...)), and a flush on _SIDE whose items
-# touch a buffer the recurrence stream has written in this backward, or name none, waits for it
-# first.  MRG_REC_STREAM=0 keeps everything on _SIDE.
-_REC_ON = [os.environ.get("MRG_REC_STREAM", "1") != "0"]
-_REC = {}          # device -> the recurrence-beside stream
-_REC_USED = {}     # device -> True once it has work in this backward
-_REC_WRITES = {}   # device -> {(ptr, nbytes)} written on it in this backward (None: unknown)
-
-
-def set_wgrad_defer(on: bool) -> bool:
-    """Enable / disable deferring side-stream weight gradients to the next recurrence; returns the old value."""
-    prev = _DEFER[0]
-    _DEFER[0] = bool(on)
-    return prev
-
-
-# --- fork points under capture.  Measured (round 4, tools/tools_fork_variants.py, tools_fork_race.py):
-# several side-stream forks from ONE point of the main stream (no main-stream node between them, e.g.
-# one fork per weight-gradient product) capture into a graph whose edges are exactly the streams'
-# order (tools/tools_capture_dot.py + tools_dot_deps.py), with no cross-stream address reuse
-# (tools/tools_capture_alias.py) and no hand-off timeout, and the eager step is bitwise right with
-# either stream delayed; yet its replay gives wrong gradients, deterministically, unless the HIP graph
-# executor runs on one queue (DEBUG_HIP_FORCE_GRAPH_QUEUES=1) or a main-stream node separates the forks.
-# So the executor mis-orders that topology (each fork's first side node has two predecessors: the
-# same main node again and the previous side node).  The guard: a fork from the main-stream point
-# the side stream already waited on adds no second wait (the side stream is ordered after that point
-# already), so the redundant edges are never captured.
-_HIP_CAPINFO = [None]
-_LAST_FORK = {}   # device -> the capture point (capture id, main-stream dependency nodes) of the last fork
-_FORK_GUARD = [os.environ.get("MRG_FORK_GUARD", "1") != "0"]   # 0: diagnostics only (tools_fork_variants.py)
-
-
-def _capture_point(stream):
-    """(capture id, the stream's current dependency node handles) while `stream` is capturing, else None."""
-    if _HIP_CAPINFO[0] is None:
-        f = ctypes.CDLL("libamdhip64.so").hipStreamGetCaptureInfo_v2
-        f.restype = ctypes.c_int
-        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_ulonglong),
-                      ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.POINTER(ctypes.c_void_p)),
-                      ctypes.POINTER(ctypes.c_size_t)]
-        _HIP_CAPINFO[0] = f
-    st, cid, graph = ctypes.c_int(0), ctypes.c_ulonglong(0), ctypes.c_void_p()
-    deps, n = ctypes.POINTER(ctypes.c_void_p)(), ctypes.c_size_t(0)
-    rc = _HIP_CAPINFO[0](ctypes.c_void_p(stream.cuda_stream), ctypes.byref(st), ctypes.byref(cid),
-                         ctypes.byref(graph), ctypes.byref(deps), ctypes.byref(n))
-    if rc != 0 or st.value != 1:   # hipStreamCaptureStatusActive
-        return None
-    return (cid.value,) + tuple(deps[i] for i in range(n.value))
-
-
-def _fork(key, s, cur):
-    """s.wait_stream(cur), skipped under capture when s already waited on cur's current point."""
-    point = _capture_point(cur) if _FORK_GUARD[0] and torch.cuda.is_current_stream_capturing() else None
-    if point is None or _LAST_FORK.get(key) != (point, s.cuda_stream):
-        s.wait_stream(cur)
-    _LAST_FORK[key] = None if point is None else (point, s.cuda_stream)
-
-
-def reset_fork_point(key=None):
-    """Forget the recorded fork point (all devices when key is None): called wherever the main and side
-    streams are joined or ordered outside _fork, and at the end of every capture (graphs.capture), so
-    the guard only ever skips a wait that an earlier _fork of the same capture really issued."""
-    if key is None:
-        _LAST_FORK.clear()
-    else:
-        _LAST_FORK.pop(key, None)
-
-
-def _ensure_join(key, cur, s, task):
-    if key not in _JOIN_PENDING:
-        def join(cur=cur, s=s, key=key):
-            _flush_deferred(key, cur.device)
-            cur.wait_stream(s)
-            if _REC_USED.pop(key, False):
-                cur.wait_stream(_REC[key])
-            _REC_WRITES.pop(key, None)
-            reset_fork_point(key)
-            _JOIN_PENDING.pop(key, None)
-            _SIDE_HOLD.pop(key, None)   # their blocks are reusable now: later work is ordered after the wait
-        torch.autograd.Variable._execution_engine.queue_callback(join)
-        _JOIN_PENDING[key] = task
-
-
-def _defers(device, rows) -> bool:
-    return (_WGRAD_SIDE[0] and _DEFER[0] and rows >= _SIDE_MIN_ROWS and _GRAD_LISTENER[0] is None
-            and torch._C._current_graph_task_id() >= 0)
-
-
-def _flush_deferred(key, device, cap=0, after=None):
-    """Issue the queued weight-gradient products on the side stream (GEMM grids capped at `cap`
-    blocks per CU while they run beside a recurrence), ordered after event `after` when given, else
-    after the current stream's work so far."""
-    items = _PENDING.pop(key, None)
-    if not items:
-        return
-    dev = torch.device(device)
-    cur = torch.cuda.current_stream(dev)
-    s = _SIDE[key]
-    if _REC_ON[0] and after is not None:
-        s = _REC.get(key)
-        if s is None:
-            s = _REC[key] = torch.cuda.Stream(device=dev)
-        _REC_USED[key] = True
-        w = _REC_WRITES.setdefault(key, set())
-        for _, _, _, writes in items:
-            if writes is None or w is None:
-                _REC_WRITES[key] = w = None
-            else:
-                w.update(writes)
-        s.wait_event(after)
-    else:
-        if _REC_USED.get(key) and _conflicts(items, _REC_WRITES.get(key, set())):
-            s.wait_stream(_REC[key])   # same gradient buffers (or unknown): keep their write order
-        if after is None:
-            _fork(key, s, cur)
-        else:
-            s.wait_event(after)
-            _LAST_FORK[key] = None
-    lib = _lib.load()
-    prev = lib.mrg_gemm_set_blocks_per_cu(cap) if cap else None
-    try:
-        with torch.cuda.stream(s):
-            for fn, keep, arith, _ in items:
-                for t in keep:
-                    if t is not None:
-                        t.record_stream(s)
-                old = _ARITH[0]
-                _ARITH[0] = arith
-                try:
-                    fn()
-                finally:
-                    _ARITH[0] = old
-    finally:
-        if cap:
-            lib.mrg_gemm_set_blocks_per_cu(prev)
-
-
-def fork_beside_recurrence(device):
-    """Called right before a backward recurrence launch: returns (the recurrence's workgroups-per-CU
-    cap: 1 when deferring, else 0; a fork mark for flush_beside_recurrence, or None)."""
-    if not (_WGRAD_SIDE[0] and _DEFER[0] and _GRAD_LISTENER[0] is None):
-        return 0, None
-    dev = torch.device(device)
-    if not _PENDING.get(dev.index or 0):
-        return 1, None
-    mark = torch.cuda.Event()
-    mark.record(torch.cuda.current_stream(dev))
-    return 1, mark
-
-
-def flush_beside_recurrence(device, mark) -> None:
-    """Called right after the recurrence launch: issues the queued weight-gradient products on the side
-    stream, ordered after `mark` (the work before the recurrence) but not after the recurrence.
-    Measured (r03, headline step, graph replay): issued BEFORE the recurrence launch the products were
-    dispatched first and delayed its start (23.06 ms/step); issued after it, 21.80.  Joining the main
-    stream to them right after (so they must finish beside this recurrence) measured 23.6: the
-    recurrence runs ~25 % slower beside them and they outlast it, so the join is left to the end of
-    the backward and the executor places them where the main stream leaves room."""
-    if mark is None:
-        return
-    _flush_deferred(torch.device(device).index or 0, device, cap=1, after=mark)
-
-
-def _writes(tensors):
-    """{(data_ptr, nbytes)} of the gradient buffers an item writes (None entries skipped)."""
-    return {(t.data_ptr(), t.numel() * t.element_size()) for t in tensors if t is not None}
-
-
-def _conflicts(items, rec_writes) -> bool:
-    """True when an item of a flush writes a buffer the recurrence stream wrote (or either is unknown)."""
-    if rec_writes is None:
-        return True
-    for _, _, _, writes in items:
-        if writes is None:
-            return True
-        for p, n in writes:
-            for q, m in rec_writes:
-                if p < q + m and q < p + n:
-                    return True
-    return False
-
-
 def _on_side(device, rows, keep, fn, writes=None):
-    """Run fn() (weight-gradient launches) on the side stream now, or queue it (see _DEFER).
-    writes: the gradient tensors fn writes (ordering across the two side streams), None = unknown."""
-    if not _defers(device, rows):
-        with _side(device, rows, keep):
-            fn()
-        return
-    dev = torch.device(device)
-    key = dev.index or 0
-    cur = torch.cuda.current_stream(dev)
-    task = torch._C._current_graph_task_id()
-    if key in _JOIN_PENDING and _JOIN_PENDING[key] != task:
-        _flush_deferred(key, dev)
-        cur.wait_stream(_SIDE[key])
-        if _REC_USED.pop(key, False):
-            cur.wait_stream(_REC[key])
-        _REC_WRITES.pop(key, None)
-        reset_fork_point(key)
-        del _JOIN_PENDING[key]
-    s = _SIDE.get(key)
-    if s is None:
-        s = _SIDE[key] = torch.cuda.Stream(device=dev)
-    _ensure_join(key, cur, s, task)
-    _PENDING.setdefault(key, []).append((fn, tuple(keep), _ARITH[0], None if writes is None else _writes(writes)))
-
-
-class _side:
-    """Issue the enclosed launches on the device's weight-gradient stream (see above)."""
-    __slots__ = ("dev", "rows", "keep", "ctx")
-
-    def __init__(self, device, rows, keep=()):
-        self.dev, self.rows, self.keep, self.ctx = device, rows, keep, None
-
-    def __enter__(self):
-        if not _WGRAD_SIDE[0]:
-            return self
-        dev = torch.device(self.dev)
-        key = dev.index or 0
-        cur = torch.cuda.current_stream(dev)
-        task = torch._C._current_graph_task_id()
-        s = _SIDE.get(key)
-        if key in _JOIN_PENDING and _JOIN_PENDING[key] != task:
-            # left over from a backward that did not finish: order after its side-stream work
-            _flush_deferred(key, dev)
-            cur.wait_stream(s)
-            if _REC_USED.pop(key, False):
-                cur.wait_stream(_REC[key])
-            _REC_WRITES.pop(key, None)
-            reset_fork_point(key)
-            del _JOIN_PENDING[key]
-        if self.rows < _SIDE_MIN_ROWS:
-            if key in _JOIN_PENDING:  # order this write after the side streams' pending ones
-                _flush_deferred(key, dev)
-                cur.wait_stream(s)
-                if _REC_USED.get(key):
-                    cur.wait_stream(_REC[key])
-                reset_fork_point(key)
-            return self
-        if task < 0:  # not inside a backward pass: stay on the current stream
-            return self
-        if s is None:
-            s = _SIDE[key] = torch.cuda.Stream(device=dev)
-        _ensure_join(key, cur, s, task)
-        _fork(key, s, cur)
-        for t in self.keep:
-            if t is not None:
-                t.record_stream(s)
-        self.ctx = torch.cuda.stream(s)
-        self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            self.ctx.__exit__(*exc)
-        return False
+    """fn() (weight-gradient launches) runs where wgrad_streams.on_side puts it, now or queued."""
+    # under the precision active here: precision(...) as a decorator enters the context around each call
+    on_side(device, rows, keep, precision(_ARITH[0])(fn), writes)
 
 
 def _wgrad(dY, ldy, X, ldx, rows, Nout, Nin, gw, device, *, dy_hi=0, dy_div=0, x_hi=0, x_div=0, gb=None,
@@ -1408,22 +1092,21 @@ class _LSTMFn(Function):
         def arr(ctype, vals):
             return (ctype * nprob)(*vals)
         VP = ctypes.c_void_p
-        cap, mark = fork_beside_recurrence(dev)
-        lib.mrg_lstm_set_blocks_per_cu(cap)
-        pr = _probe("lstm_bwd", 8.0 * H * H * B * T * nprob).__enter__()  # dG W_hh FLOPs
-        rc = lib.mrg_lstm_bwd(
-            nprob, B, T, H,
-            arr(VP, [_ptr(p[2]) for p in per]), arr(VP, [_ptr(p[5]) for p in per]),
-            arr(VP, [_ptr(p[6]) for p in per]), arr(VP, [_ptr(p[8]) for p in per]),
-            arr(VP, dy_ptr), arr(ctypes.c_long, dy_bs), arr(ctypes.c_long, dy_ts),
-            arr(VP, [_ptr(t) for t in dhT]), arr(VP, [_ptr(t) for t in dcT]),
-            arr(VP, [_ptr(t) for t in dG]), arr(VP, [_ptr(t) for t in dh0]),
-            arr(VP, [_ptr(t) for t in dc0]), arr(ctypes.c_int, [int(r) for r in reverse]),
-            arr(VP, [_ptr(xbuf[i]) for i in range(nprob)]), None, _ptr(_err_flag(dev)),
-            _lib.cu_count(dev.index or 0), force_bs, _stream())
-        pr.__exit__()
-        _lib.check(rc, "lstm bwd")
-        flush_beside_recurrence(dev, mark)
+        with beside_recurrence(dev) as cap:
+            lib.mrg_lstm_set_blocks_per_cu(cap)
+            pr = _probe("lstm_bwd", 8.0 * H * H * B * T * nprob).__enter__()  # dG W_hh FLOPs
+            rc = lib.mrg_lstm_bwd(
+                nprob, B, T, H,
+                arr(VP, [_ptr(p[2]) for p in per]), arr(VP, [_ptr(p[5]) for p in per]),
+                arr(VP, [_ptr(p[6]) for p in per]), arr(VP, [_ptr(p[8]) for p in per]),
+                arr(VP, dy_ptr), arr(ctypes.c_long, dy_bs), arr(ctypes.c_long, dy_ts),
+                arr(VP, [_ptr(t) for t in dhT]), arr(VP, [_ptr(t) for t in dcT]),
+                arr(VP, [_ptr(t) for t in dG]), arr(VP, [_ptr(t) for t in dh0]),
+                arr(VP, [_ptr(t) for t in dc0]), arr(ctypes.c_int, [int(r) for r in reverse]),
+                arr(VP, [_ptr(xbuf[i]) for i in range(nprob)]), None, _ptr(_err_flag(dev)),
+                _lib.cu_count(dev.index or 0), force_bs, _stream())
+            pr.__exit__()
+            _lib.check(rc, "lstm bwd")
 
         out = [None]
         dx_of = {}   # first problem of each shared x -> its dx (the others add into it)
@@ -1684,15 +1367,14 @@ class _GRUFn(Function):
         if ctx.persist:
             xb = zeros(max(1, lib.mrg_gru_xbuf_bytes(B, H) // 8), dtype=torch.int64, device=dev)
             dh_next = torch.empty(B, H, device=dev, dtype=torch.float32) if (h0c is not None and need[6]) else None
-            # deferred weight gradients (functional._DEFER) run beside this recurrence, as beside the LSTM's
-            _cap, mark = fork_beside_recurrence(dev)
-            with _probe("gru_bwd", 6.0 * H * H * B * T):
-                rc = lib.mrg_gru_bwd(B, T, H, _ptr(w_hh), _ptr(gates), T * H3, H3, _ptr(ghn), T * H, H, _ptr(y), T * H,
-                                     H, _ptr(h0c), _ptr(dy), T * H, H, _ptr(None if dhT is None else dhT.contiguous()),
-                                     _ptr(dGX), _ptr(dGH), T * H3, H3, _ptr(dh_next), int(reverse), _ptr(xb),
-                                     _ptr(_err_flag(dev)), _lib.cu_count(dev.index or 0), _stream())
-            _lib.check(rc, "gru bwd")
-            flush_beside_recurrence(dev, mark)
+            # deferred weight gradients (wgrad_streams._DEFER) run beside this recurrence, as beside the LSTM's
+            with beside_recurrence(dev):
+                with _probe("gru_bwd", 6.0 * H * H * B * T):
+                    rc = lib.mrg_gru_bwd(B, T, H, _ptr(w_hh), _ptr(gates), T * H3, H3, _ptr(ghn), T * H, H, _ptr(y), T * H,
+                                         H, _ptr(h0c), _ptr(dy), T * H, H, _ptr(None if dhT is None else dhT.contiguous()),
+                                         _ptr(dGX), _ptr(dGH), T * H3, H3, _ptr(dh_next), int(reverse), _ptr(xb),
+                                         _ptr(_err_flag(dev)), _lib.cu_count(dev.index or 0), _stream())
+                _lib.check(rc, "gru bwd")
         for t in ((range(T) if reverse else range(T - 1, -1, -1)) if not ctx.persist else ()):
             pt = t + 1 if reverse else t - 1
             if 0 <= pt < T:

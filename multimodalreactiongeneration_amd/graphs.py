@@ -35,7 +35,7 @@ def capture(step: Callable[[], object], warmup: int = 2, preserve: Sequence[torc
         with torch.cuda.graph(graph):
             step()
     finally:
-        Fn.reset_fork_point()   # fork points are per capture (functional._fork's guard)
+        Fn.reset_fork_point()   # fork points are per capture (wgrad_streams._fork's guard)
     with torch.no_grad():
         for t, v in zip(preserve, saved):
             t.copy_(v)

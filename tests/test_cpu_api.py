@@ -246,7 +246,7 @@ def test_kv_sink_refuses_stale_sum_from_an_earlier_backward():
 
 
 def test_side_stream_flush_conflicts():
-    """functional._conflicts: a flush on the side stream waits for the recurrence stream when one of its
+    """wgrad_streams._conflicts: a flush on the side stream waits for the recurrence stream when one of its
     items writes a gradient buffer the recurrence stream wrote in this backward, or names none."""
     from multimodalreactiongeneration_amd import functional as Fn
     a, b = torch.zeros(64), torch.zeros(64)

@@ -1,8 +1,8 @@
-"""HIP-graph capture invariants the training step relies on (graphs.capture, functional._side).
+"""HIP-graph capture invariants the training step relies on (graphs.capture, wgrad_streams.side).
 
 The replayed step forks weight-gradient work onto a side stream in two ways: ``wait_stream`` (fork at
-the current point of the main stream, functional._side) and ``wait_event(mark)`` with a mark recorded
-BEFORE the next backward recurrence's launch (functional.flush_beside_recurrence).  Both must keep the
+the current point of the main stream, wgrad_streams.side) and ``wait_event(mark)`` with a mark recorded
+BEFORE the next backward recurrence's launch (wgrad_streams.beside_recurrence).  Both must keep the
 side stream's own order across consecutive forks in the captured graph (later products accumulate into
 the same gradient buffers and reuse split-K scratch), whatever the timing: a 20 ms busy kernel makes a
 missing edge visible.  The model-level cases replay the whole lstmformer step with one fork per layer
@@ -64,7 +64,7 @@ def test_capture_keeps_side_stream_order_across_forks(pattern):
 
 
 def test_fork_guard_with_side_only_work_between_same_point_forks():
-    """functional._fork's capture guard (skip a second wait on a main-stream point the side stream
+    """wgrad_streams._fork's capture guard (skip a second wait on a main-stream point the side stream
     already waited on) with side-stream-only work issued OUTSIDE _fork between two forks from the same
     point, and a join that resets the point: main: x = 1 | fork -> side: busy 20 ms,
     y = x + 1 | side only (no fork): u = y * 2 | fork again, same main point (wait skipped) -> side:
@@ -96,7 +96,7 @@ def test_fork_guard_with_side_only_work_between_same_point_forks():
             with torch.cuda.stream(side):
                 torch.add(u, x, out=z)
             cur.wait_stream(side)
-            Fn.reset_fork_point(key)                  # what every join in functional does
+            Fn.reset_fork_point(key)                  # what every join in wgrad_streams does
             torch.add(z, 1.0, out=w)
             Fn._fork(key, side, cur)
             with torch.cuda.stream(side):
@@ -119,7 +119,7 @@ def test_replayed_step_bitwise_eager_fork_patterns(split, defer):
     eager one, with one side-stream fork per encoder layer (default) and with one fork per product
     (encoder_stack.SPLIT_FORKS), weight gradients deferred beside the backward recurrences (default)
     or forked where they are ready.  (True, False) is the pattern whose replay was wrong before the
-    fork-point guard (functional._fork: several forks from one main-stream point)."""
+    fork-point guard (wgrad_streams._fork: several forks from one main-stream point)."""
     from multimodalreactiongeneration_amd import configs as C
     from multimodalreactiongeneration_amd import encoder_stack as ES
     from multimodalreactiongeneration_amd import functional as Fn
@@ -151,5 +151,104 @@ def test_replayed_step_bitwise_eager_fork_patterns(split, defer):
             assert torch.equal(opt.flat_grad, ref)
     finally:
         ES.SPLIT_FORKS = prev
+        Fn.set_wgrad_stream(prev_side)
+        Fn.set_wgrad_defer(prev_defer)
+
+
+class _RaiseInBackward(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        return x.clone()
+
+    @staticmethod
+    def backward(ctx, dy):
+        raise RuntimeError("raised in backward on purpose")
+
+
+def _linear_grad(w, xs, gs, first=None):
+    """w.grad of sum_i <linear(xs[i], w), gs[i]> (one graph, created in the given order); `first`
+    wraps the first input (an earlier-created node runs later in the backward)."""
+    from multimodalreactiongeneration_amd import functional as Fn
+    ys = [Fn.linear(x if first is None or i else first(x), w) for i, x in enumerate(xs)]
+    sum((y * g).sum() for y, g in zip(ys, gs)).backward()
+
+
+@pytest.mark.parametrize("defer", [True, False])
+def test_backward_that_raised_leaves_no_stale_join(defer):
+    """A backward that raised after the linear forked (or queued) its weight gradient never ran its
+    end-of-backward join.  The next backward on the same parameter must order itself after that
+    left-over side-stream work and join again: w.grad (read on the main stream right after
+    backward(), and after a synchronize) is bitwise the single-stream one."""
+    from multimodalreactiongeneration_amd import functional as Fn
+    torch.manual_seed(3)
+    w = torch.randn(64, 64, device=DEV, requires_grad=True)
+    x = torch.randn(Fn._SIDE_MIN_ROWS, 64, device=DEV, requires_grad=True)   # 2048 rows: the smallest that forks
+    g = torch.randn(Fn._SIDE_MIN_ROWS, 64, device=DEV)
+    prev_side, prev_defer = Fn.set_wgrad_stream(False), Fn.set_wgrad_defer(defer)
+    try:
+        _linear_grad(w, [x], [g])
+        torch.cuda.synchronize()
+        ref = w.grad.clone()
+        assert ref.abs().max().item() > 0
+        w.grad = None
+        Fn.set_wgrad_stream(True)
+        with pytest.raises(RuntimeError, match="raised in backward on purpose"):
+            _linear_grad(w, [x], [g], first=_RaiseInBackward.apply)   # linear's backward runs, then the raise
+        stale = w.grad    # stays allocated: the left-over product may still be writing it
+        w.grad = None
+        _linear_grad(w, [x], [g])
+        on_main = w.grad.clone()
+        torch.cuda.synchronize()
+        Fn.check_errors()
+        assert torch.equal(on_main, ref)
+        assert torch.equal(w.grad, ref)
+        del stale
+    finally:
+        Fn.set_wgrad_stream(prev_side)
+        Fn.set_wgrad_defer(prev_defer)
+
+
+@pytest.mark.parametrize("captured", [False, True])
+@pytest.mark.parametrize("defer", [True, False])
+@pytest.mark.parametrize("few_rows_first", [False, True])
+def test_few_row_write_ordered_behind_pending_side_work(few_rows_first, defer, captured):
+    """One parameter used by a 4096-row linear (forked or queued) and a 64-row one (issued on the
+    current stream) in one graph, in both creation orders: the few-row write is ordered with the side
+    streams' pending ones, so w.grad is bitwise the single-stream one, eager and replayed."""
+    from multimodalreactiongeneration_amd import functional as Fn
+    from multimodalreactiongeneration_amd.graphs import capture
+    torch.manual_seed(4)
+    w = torch.randn(64, 64, device=DEV, requires_grad=True)
+    rows = [64, 4096] if few_rows_first else [4096, 64]
+    xs = [torch.randn(r, 64, device=DEV) for r in rows]
+    gs = [torch.randn(r, 64, device=DEV) for r in rows]
+    w.grad = torch.zeros_like(w)
+
+    def step():
+        w.grad.zero_()
+        _linear_grad(w, xs, gs)
+    prev_side, prev_defer = Fn.set_wgrad_stream(False), Fn.set_wgrad_defer(defer)
+    try:
+        step()
+        torch.cuda.synchronize()
+        ref = w.grad.clone()
+        assert ref.abs().max().item() > 0
+        Fn.set_wgrad_stream(True)
+        if not captured:
+            step()
+            on_main = w.grad.clone()
+            torch.cuda.synchronize()
+            Fn.check_errors()
+            assert torch.equal(on_main, ref)
+            assert torch.equal(w.grad, ref)
+            return
+        replay = capture(step, 1)
+        for _ in range(2):
+            w.grad.fill_(-1.0)
+            replay()
+            torch.cuda.synchronize()
+            Fn.check_errors()
+            assert torch.equal(w.grad, ref)
+    finally:
         Fn.set_wgrad_stream(prev_side)
         Fn.set_wgrad_defer(prev_defer)

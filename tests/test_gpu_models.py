@@ -260,7 +260,7 @@ def test_metaformer_generation_benchmark_width_vs_oracle():
 
 @pytest.mark.parametrize("defer,B", [(False, 8), (True, 64)])
 def test_wgrad_side_stream_bitwise(defer, B):
-    """Weight gradients on the side stream (functional._side), eager and graph-replayed, give the
+    """Weight gradients on the side stream (wgrad_streams.side), eager and graph-replayed, give the
     bit-identical gradients of the single-stream schedule (every kernel is deterministic).  With
     deferral the products run beside the next backward recurrence, which then takes one workgroup
     per CU (batch tile 4 instead of 2 at B = 64): the gradients are still bitwise the same."""

@@ -2,7 +2,7 @@
 the main stream?  Main stream: NM busy kernels of US microseconds each (mrg_debug_busy, 1 workgroup
 so the side fits beside it).  Side work: after main kernel k of each fork point k in FORKS, NS busy
 kernels, issued either on ONE side stream (a single chain with several incoming edges: the
-production pattern of functional._flush_deferred) or on a fresh stream per fork point (each branch
+production pattern of wgrad_streams._flush_deferred) or on a fresh stream per fork point (each branch
 one incoming and one outgoing edge).  Joined at the end.  Prints, per replay, each side kernel's
 start relative to the step's start, from HIP events (eager) -- run under
 `rocprofv3 --kernel-trace` for the replayed graph's real timeline.

@@ -10,14 +10,15 @@ import traceback
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # repo root
-from multimodalreactiongeneration_amd import configs as C, functional as Fn  # noqa: E402
+from multimodalreactiongeneration_amd import configs as C, functional as Fn, wgrad_streams as WS  # noqa: E402
 from multimodalreactiongeneration_amd.model import Metaformer  # noqa: E402
 from multimodalreactiongeneration_amd.synthetic import make_batch  # noqa: E402
 
 
 def where():
     for fr in reversed(traceback.extract_stack()[:-2]):
-        if "multimodalreactiongeneration_amd" in fr.filename and "functional.py" not in fr.filename:
+        if ("multimodalreactiongeneration_amd" in fr.filename
+                and os.path.basename(fr.filename) not in ("functional.py", "wgrad_streams.py")):
             return f"{os.path.basename(fr.filename)}:{fr.lineno} {fr.name}"
     fr = traceback.extract_stack()[-3]
     return f"{os.path.basename(fr.filename)}:{fr.lineno} {fr.name}"
@@ -30,26 +31,27 @@ def main():
     model = Metaformer(mc, oc, me).to(dev)
     batch = make_batch(B=64, T=300, seed=1234, device=dev)
     log = []
-    orig_on_side, orig_flush, orig_fork = Fn._on_side, Fn._flush_deferred, Fn.fork_beside_recurrence
+    orig_on_side, orig_flush, orig_bracket = Fn._on_side, WS._flush_deferred, WS.beside_recurrence
 
-    def on_side(device, rows, keep, fn):
-        log.append(f"queue  rows={rows} defer={Fn._defers(device, rows)} from {where()}")
-        return orig_on_side(device, rows, keep, fn)
+    def on_side(device, rows, keep, fn, writes=None):
+        log.append(f"queue  rows={rows} defer={WS._defers(device, rows)} from {where()}")
+        return orig_on_side(device, rows, keep, fn, writes=writes)
 
     def flush(key, device, cap=0, after=None):
-        n = len(Fn._PENDING.get(key, []) or [])
+        n = len(WS._STATES[key].pending)
         log.append(f"FLUSH  {n} products cap={cap} beside={'yes' if after is not None else 'no'} from {where()}")
         return orig_flush(key, device, cap, after)
 
-    def fork(device):
-        r = orig_fork(device)
-        log.append(f"fork   pending={len(Fn._PENDING.get(0, []) or [])} -> {r[0]}, mark={r[1] is not None} from {where()}")
-        return r
-    Fn._on_side, Fn._flush_deferred, Fn.fork_beside_recurrence = on_side, flush, fork
+    def bracket(device):
+        log.append(f"recurrence pending={len(WS._STATES[torch.device(device).index or 0].pending)} from {where()}")
+        return orig_bracket(device)
+    Fn._on_side, WS._flush_deferred = on_side, flush
     from multimodalreactiongeneration_amd import encoder_stack, integrate
     for mod in (encoder_stack, integrate):
         if hasattr(mod, "_on_side"):
             mod._on_side = on_side
+    for mod in (Fn, encoder_stack):
+        mod.beside_recurrence = bracket
     for it in range(2):
         log.clear()
         loss = model.training_step(list(batch))["loss"]
