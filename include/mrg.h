@@ -575,6 +575,17 @@ int mrg_adamw_step(float* params, const float* grads, float* exp_avg, float* exp
                    float* step_lr, float weight_decay, float beta1, float beta2, float eps,
                    const int* err, hipStream_t stream);
 
+/* ---------------------------------------------------------------- SGD
+ * torch.optim.SGD(lr, momentum, weight_decay) step over flat buffers, dampening = 0 and
+ * nesterov = False (configure_optimizers, lstmformer.py:334-340).  Per element
+ * g = grad + weight_decay * p; with momentum != 0, buf = g when step_lr[0] == 0 (torch seeds the
+ * buffer with the first gradient) and buf = momentum * buf + g afterwards, then p -= lr * buf;
+ * with momentum == 0, p -= lr * g and momentum_buf (which may then be null) is not touched.
+ * step_lr and err as in mrg_adamw_step: lr and the step count are read on the device, the count
+ * is incremented after the update, and a set err skips both.  n == 0 only counts the step.    */
+int mrg_sgd_step(float* params, const float* grads, float* momentum_buf, long n, float* step_lr,
+                 float weight_decay, float momentum, const int* err, hipStream_t stream);
+
 /* ---------------------------------------------------------------- features (data loader)
  * AudioPreprocessor (mr_gen/utils/preprocess/audio.py:6-67).  The power spectrum comes from one
  * GEMM of the frames (read in place from the waveform, row stride `hop`) with the windowed DFT

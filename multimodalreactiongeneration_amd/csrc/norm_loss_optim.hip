@@ -569,6 +569,30 @@ __global__ void adamw_step_inc_kernel(float* step_lr, const int* err) {
   if (!(err && *err)) step_lr[0] += 1.0f;
 }
 
+// ------------------------------------------------------------------ SGD
+// torch.optim.SGD(lr, momentum, weight_decay) with dampening = 0, nesterov = False (lstmformer.py:334-340),
+// one launch over the flat buffers.  The first step seeds the buffer with g (torch clones the gradient),
+// decided on the device step count so a captured graph replays the right branch; err as in adamw_kernel.
+// MOM = false (momentum == 0) never reads or writes buf.
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                  float* __restrict__ buf, long n,
+                                                  const float* __restrict__ step_lr, float wd, float mom,
+                                                  const int* __restrict__ err) {
+  if (err && *err) return;
+  const bool first = step_lr[0] == 0.0f;
+  const float lr = step_lr[1];
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    float pi = p[i];
+    float gi = g[i] + wd * pi;
+    if (MOM) {
+      gi = first ? gi : mom * buf[i] + gi;
+      buf[i] = gi;
+    }
+    p[i] = pi - lr * gi;
+  }
+}
+
 }  // namespace mrg
 
 using namespace mrg;
@@ -907,6 +931,27 @@ MRG_API int mrg_adamw_step(float* params, const float* grads, float* exp_avg, fl
     adamw_kernel<<<grid, 256, 0, stream>>>(params, grads, exp_avg, exp_avg_sq, n, step_lr, weight_decay,
                                            beta1, beta2, eps, err);
     if (check_launch("adamw_kernel")) return 1;
+  }
+  adamw_step_inc_kernel<<<1, 1, 0, stream>>>(step_lr, err);
+  return check_launch("adamw_step_inc_kernel");
+}
+
+// step_lr, err: as mrg_adamw_step.  momentum_buf may be null iff momentum == 0.
+MRG_API int mrg_sgd_step(float* params, const float* grads, float* momentum_buf, long n, float* step_lr,
+                         float weight_decay, float momentum, const int* err, hipStream_t stream) {
+  MRG_REQUIRE(n >= 0, "mrg_sgd_step: n = %ld", n);
+  MRG_REQUIRE(momentum == 0.0f || momentum_buf != nullptr || n == 0,
+              "mrg_sgd_step: momentum %g needs a momentum buffer", (double)momentum);
+  if (n > 0) {
+    long nb = (n + 255) / 256;
+    int grid = (int)(nb < 4096 ? nb : 4096);
+    if (momentum != 0.0f)
+      sgd_kernel<true><<<grid, 256, 0, stream>>>(params, grads, momentum_buf, n, step_lr, weight_decay,
+                                                 momentum, err);
+    else
+      sgd_kernel<false><<<grid, 256, 0, stream>>>(params, grads, nullptr, n, step_lr, weight_decay, 0.0f,
+                                                  err);
+    if (check_launch("sgd_kernel")) return 1;
   }
   adamw_step_inc_kernel<<<1, 1, 0, stream>>>(step_lr, err);
   return check_launch("adamw_step_inc_kernel");

@@ -35,7 +35,7 @@ from torch import nn
 from .. import functional as Fn
 from ..configs import as_attr
 from ..metrics import MultiTargetMetrics
-from ..optim import FusedAdamW
+from ..optim import FusedAdamW, FusedSGD
 from .layers import (Linear, LSTMSampler, LSTMLayerd, MultimodalAttention, ResidualConnection, paired_lstm_layerd,
                      run_sequential_ffn)
 from .masks import gen_attention_mask
@@ -99,9 +99,8 @@ class LightningSurface(nn.Module):
         if optim.use_optimizer == "adam":
             opt = FusedAdamW(self.parameters(), lr=optim.lr, weight_decay=optim.weight_decay)
         elif optim.use_optimizer == "sgd":
-            # off the benchmarked path (SURVEY §8a13 uses AdamW); plain torch optimizer
-            opt = torch.optim.SGD(self.parameters(), lr=optim.lr, momentum=optim.momentum,
-                                  weight_decay=optim.weight_decay)
+            opt = FusedSGD(self.parameters(), lr=optim.lr, momentum=optim.momentum,
+                           weight_decay=optim.weight_decay)
         else:
             raise ValueError("invalid optimizer type")
         self.optimizer = opt

@@ -1,20 +1,26 @@
-"""Fused AdamW over one flat parameter buffer (one libmrg launch per step).
+"""Fused AdamW and SGD over one flat parameter buffer (one libmrg launch per step).
 
-Stands in for ``torch.optim.AdamW(self.parameters(), lr, weight_decay)`` of
-``configure_optimizers`` (lstmformer.py:327-333, lstm_with_sample.py:248-254,
-simple_lstm.py:193-199).  On construction every parameter is re-pointed into a
+Stand in for ``torch.optim.AdamW(self.parameters(), lr, weight_decay)`` and
+``torch.optim.SGD(self.parameters(), lr, momentum, weight_decay)`` of
+``configure_optimizers`` (lstmformer.py:327-342, lstm_with_sample.py:248-263,
+simple_lstm.py:193-208).  On construction every parameter is re-pointed into a
 contiguous fp32 buffer and its ``.grad`` into a twin gradient buffer, so
 ``step()`` is a single kernel, ``zero_grad()`` a single memset and the DDP
 reducer (``ddp.GradReducer``) all-reduces the gradient buffer in place.
-It subclasses ``torch.optim.Optimizer`` so torch LR schedulers
+They subclass ``torch.optim.Optimizer`` so torch LR schedulers
 (CosineAnnealingLR) drive ``param_groups[0]['lr']``: the group is a dict whose
 ``'lr'`` assignment also writes the device-side LR the kernel reads, so a
 scheduler stepped between HIP-graph replays takes effect in the replayed step.
 
 Error surfacing: the persistent LSTM kernels OR a device flag on a hand-off
-timeout; the AdamW kernel reads it and skips the update (garbage gradients never
+timeout; the update kernel reads it and skips the update (garbage gradients never
 reach the weights, replayed graphs included), and ``step()`` raises at the next
 step once the flag, copied to pinned host memory without a sync, reads non-zero.
+
+Checkpoints: ``state_dict()`` / ``load_state_dict()`` speak the layout of the torch
+optimizer of the same name (per-parameter entries keyed by the parameter's index),
+sliced out of / copied into the flat buffers, so a Lightning ``optimizer_states``
+entry written by either side resumes on the other.
 """
 from __future__ import annotations
 
@@ -58,36 +64,44 @@ class _LRGroup(dict):
             self._opt._write_lr(v)
 
 
-class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What the fused optimizers share: the flat parameter / gradient buffers, the device-side
+    {completed steps, lr} pair, the asynchronous error check and the torch-layout state_dict.
+
+    A subclass names its update (``_UPDATE``, for the error message), lists its per-parameter state
+    (``_moments()``: torch's state key -> flat buffer) and refuses group options its kernel does not
+    implement (``_check_group``)."""
+
+    _UPDATE = ""
+
+    def __init__(self, params: Iterable, defaults):
         params = list(params)
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self.flat, self.flat_grad, self.plist = flatten_parameters(params)
-        dev = self.flat.device
-        self.exp_avg = torch.zeros_like(self.flat)
-        self.exp_avg_sq = torch.zeros_like(self.flat)
-        self.step_lr = torch.tensor([0.0, float(lr)], dtype=torch.float32, device=dev)
-        self._lr_on_device = float(lr)
+        super().__init__(params, defaults)
+        if len(self.param_groups) != 1:
+            raise ValueError(f"{type(self).__name__} takes one param group (one flat buffer, one device-side LR)")
+        self._check_group(self.param_groups[0])
+        self._all = list(self.param_groups[0]["params"])   # frozen parameters included: torch's indices
+        self.flat, self.flat_grad, self.plist = flatten_parameters(self._all)
+        lr = float(self.param_groups[0]["lr"])
+        self.step_lr = torch.tensor([0.0, lr], dtype=torch.float32, device=self.flat.device)
+        self._lr_on_device = lr
         self._wrap_groups()
         self._err_host = self._err_event = None
 
+    def _check_group(self, group):
+        pass
+
+    def _moments(self):
+        return {}
+
     def _wrap_groups(self):
         self.param_groups[0] = _LRGroup(self.param_groups[0], self)
-
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        self._wrap_groups()
-        self._write_lr(self.param_groups[0]["lr"])
 
     def _write_lr(self, lr):
         lr = float(lr)
         if lr != self._lr_on_device:
             self.step_lr[1].fill_(lr)  # stream-ordered: lands before the next (replayed) step
             self._lr_on_device = lr
-
-    def state_tensors(self):
-        """Device state one update changes (graphs.capture(preserve=...) restores it after warm-up)."""
-        return [self.flat, self.exp_avg, self.exp_avg_sq, self.step_lr]
 
     def _check_async(self):
         """Raise if an earlier step's persistent kernels reported a hand-off timeout (no sync: the
@@ -102,24 +116,21 @@ class FusedAdamW(torch.optim.Optimizer):
             self._err_host.zero_()
             err.zero_()
             raise RuntimeError("libmrg: LSTM recurrence hand-off timed out (grid not co-resident?); "
-                               "the AdamW update of that step was skipped")
+                               f"the {self._UPDATE} update of that step was skipped")
         self._err_host.copy_(err, non_blocking=True)
         self._err_event.record()
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
+    def _begin_step(self):
+        """The param group of this step, after the LR write and the error check every step starts with."""
+        _lib.require_device(self.flat)
         g = self.param_groups[0]
         self._write_lr(g["lr"])
         self._check_async()
-        b1, b2 = g["betas"]
-        _lib.check(_lib.load().mrg_adamw_step(
-            _ptr(self.flat), _ptr(self.flat_grad), _ptr(self.exp_avg), _ptr(self.exp_avg_sq),
-            self.flat.numel(), _ptr(self.step_lr), float(g["weight_decay"]), float(b1), float(b2),
-            float(g["eps"]), _ptr(_err_flag(self.flat.device)), _stream()), "adamw")
+        return g
+
+    def _end_step(self):
         from . import functional as Fn
         Fn.invalidate_weight_planes()  # the weights changed: their bf16 planes are stale
-        return loss
 
     def zero_grad(self, set_to_none: bool = False):
         # gradients stay views of the flat buffer (set_to_none would detach them from it)
@@ -128,3 +139,172 @@ class FusedAdamW(torch.optim.Optimizer):
             Fn.zero_(self.flat_grad)
         else:
             self.flat_grad.zero_()
+
+    # ---- state in torch's layout
+    def _slices(self):
+        """(index among all parameters passed in, offset into the flat buffers, parameter) per trainable one."""
+        out, off = [], 0
+        for i, p in enumerate(self._all):
+            if p.requires_grad:
+                out.append((i, off, p))
+                off += p.numel()
+        return out
+
+    def _entry(self, steps, tensors):
+        """One parameter's state entry from its slices of _moments() (torch's keys, torch's order)."""
+        return tensors
+
+    def state_dict(self):
+        sd = super().state_dict()   # param_groups with indices over every parameter; self.state is empty
+        steps = float(self.step_lr[0])   # one device read: a checkpoint-time call, never inside a capture
+        moments = self._moments()
+        state = {}
+        if steps > 0 and moments:
+            for i, off, p in self._slices():
+                state[i] = self._entry(steps, {k: buf[off:off + p.numel()].clone().view(p.shape)
+                                               for k, buf in moments.items()})
+        sd["state"] = state
+        return sd
+
+    def _steps_of(self, entries):
+        """The completed-step count a loaded state stands for (entries: index -> {key: tensor})."""
+        raise NotImplementedError
+
+    def load_state_dict(self, state_dict):
+        groups = state_dict["param_groups"]
+        if len(groups) != 1:
+            raise ValueError("loaded state dict has a different number of parameter groups")
+        merged = dict(self.defaults)
+        merged.update(groups[0])
+        self._check_group(merged)
+        slices = {i: (off, p) for i, off, p in self._slices()}
+        keys = list(self._moments_for(merged))
+        entries = {}
+        for k, st in state_dict["state"].items():
+            tensors = {name: st[name] for name in keys if st.get(name) is not None}
+            if not tensors and "step" not in st:
+                continue   # torch.optim.SGD without momentum leaves empty entries
+            i = int(k)
+            if i not in slices:
+                raise ValueError(f"optimizer state for parameter {i}, which is not a trainable parameter here")
+            if len(tensors) != len(keys):
+                raise ValueError(f"optimizer state of parameter {i} lacks {sorted(set(keys) - set(tensors))}")
+            for name, t in tensors.items():
+                if tuple(t.shape) != tuple(slices[i][1].shape):
+                    raise ValueError(f"optimizer state {name!r} of parameter {i} has shape {tuple(t.shape)}, "
+                                     f"the parameter {tuple(slices[i][1].shape)}")
+            entries[i] = dict(st)
+        steps = self._steps_of(entries)
+        # everything is checked: now the groups (torch restores them), then the flat buffers in place
+        super().load_state_dict({"state": {}, "param_groups": [merged]})
+        self._wrap_groups()
+        self._write_lr(self.param_groups[0]["lr"])
+        self._fit_moments(self.param_groups[0])
+        with torch.no_grad():
+            for name, buf in self._moments().items():
+                buf.zero_()
+                for i, st in entries.items():
+                    off, p = slices[i]
+                    buf[off:off + p.numel()].copy_(st[name].detach().reshape(-1))
+            self.step_lr[0].fill_(float(steps))
+
+    def _moments_for(self, group):
+        """The state keys a param group with these options carries."""
+        return self._moments()
+
+    def _fit_moments(self, group):
+        """Make the moment buffers fit a freshly loaded group."""
+
+
+class FusedAdamW(_FlatOptimizer):
+    _UPDATE = "AdamW"
+
+    def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
+                                      maximize=False, decoupled_weight_decay=True))
+        self.exp_avg = torch.zeros_like(self.flat)
+        self.exp_avg_sq = torch.zeros_like(self.flat)
+
+    def _check_group(self, group):
+        if group.get("amsgrad") or group.get("maximize") or not group.get("decoupled_weight_decay", True):
+            raise ValueError("FusedAdamW implements torch.optim.AdamW without amsgrad / maximize")
+
+    def _moments(self):
+        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
+
+    def _entry(self, steps, tensors):
+        return {"step": torch.tensor(steps, dtype=torch.float32), **tensors}
+
+    def _steps_of(self, entries):
+        if any("step" not in st for st in entries.values()):
+            raise ValueError("FusedAdamW: a state entry has moments but no 'step'")
+        steps = {float(st["step"]) for st in entries.values()}
+        if len(steps) > 1:
+            raise ValueError(f"FusedAdamW keeps one step count for all parameters; the state has {sorted(steps)}")
+        return steps.pop() if steps else 0.0
+
+    def state_tensors(self):
+        """Device state one update changes (graphs.capture(preserve=...) restores it after warm-up)."""
+        return [self.flat, self.exp_avg, self.exp_avg_sq, self.step_lr]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        g = self._begin_step()
+        b1, b2 = g["betas"]
+        _lib.check(_lib.load().mrg_adamw_step(
+            _ptr(self.flat), _ptr(self.flat_grad), _ptr(self.exp_avg), _ptr(self.exp_avg_sq),
+            self.flat.numel(), _ptr(self.step_lr), float(g["weight_decay"]), float(b1), float(b2),
+            float(g["eps"]), _ptr(_err_flag(self.flat.device)), _stream()), "adamw")
+        self._end_step()
+        return loss
+
+
+class FusedSGD(_FlatOptimizer):
+    """torch.optim.SGD(lr, momentum, weight_decay) with dampening = 0 and nesterov = False (mrg_sgd_step)."""
+
+    _UPDATE = "SGD"
+
+    def __init__(self, params: Iterable, lr, momentum=0.0, weight_decay=0.0, dampening=0.0, nesterov=False,
+                 maximize=False):
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                      nesterov=nesterov, maximize=maximize))
+        self.momentum_buf = None
+        self._fit_moments(self.param_groups[0])
+
+    def _check_group(self, group):
+        if group.get("dampening") or group.get("nesterov") or group.get("maximize"):
+            raise ValueError("FusedSGD implements torch.optim.SGD without dampening / nesterov / maximize")
+        if group["momentum"] < 0 or group["weight_decay"] < 0:
+            raise ValueError(f"FusedSGD: negative momentum {group['momentum']} or weight_decay "
+                             f"{group['weight_decay']}")
+
+    def _moments(self):
+        return {} if self.momentum_buf is None else {"momentum_buffer": self.momentum_buf}
+
+    def _moments_for(self, group):
+        return ["momentum_buffer"] if group["momentum"] != 0 else []
+
+    def _fit_moments(self, group):
+        if group["momentum"] == 0:
+            self.momentum_buf = None
+        elif self.momentum_buf is None:
+            self.momentum_buf = torch.zeros_like(self.flat)
+
+    def _steps_of(self, entries):
+        return 1.0 if entries else 0.0   # the kernel only asks whether the buffer has been seeded
+
+    def state_tensors(self):
+        """Device state one update changes (graphs.capture(preserve=...) restores it after warm-up)."""
+        return [t for t in (self.flat, self.momentum_buf, self.step_lr) if t is not None]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        g = self._begin_step()
+        _lib.check(_lib.load().mrg_sgd_step(
+            _ptr(self.flat), _ptr(self.flat_grad), _ptr(self.momentum_buf), self.flat.numel(),
+            _ptr(self.step_lr), float(g["weight_decay"]), float(g["momentum"]),
+            _ptr(_err_flag(self.flat.device)), _stream()), "sgd")
+        self._end_step()
+        return loss
