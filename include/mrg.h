@@ -586,6 +586,24 @@ int mrg_adamw_step(float* params, const float* grads, float* exp_avg, float* exp
 int mrg_sgd_step(float* params, const float* grads, float* momentum_buf, long n, float* step_lr,
                  float weight_decay, float momentum, const int* err, hipStream_t stream);
 
+/* ---------------------------------------------------------------- gradient clipping
+ * Lightning's trainer.gradient_clip_val over the flat gradient buffer, in place, before the update.
+ * mrg_grad_clip_norm (gradient_clip_algorithm: norm) is torch.nn.utils.clip_grad_norm_ with
+ * norm_type = 2, error_if_nonfinite = False: three launches (per-block partial sums of squares into
+ * ws, a one-block final in double, the scale), no atomics, no host read.  clip_state: device
+ * float[2], overwritten: [0] the total norm before clipping, [1] the coefficient
+ * min(1, max_norm / (norm + 1e-6f)); the scale launch returns at once when the coefficient is >= 1
+ * (decided on the device, so a replayed graph clips by that replay's gradients).  A NaN norm gives
+ * a NaN coefficient and NaN gradients, as torch; max_norm = +inf only measures.  ws:
+ * mrg_grad_clip_workspace_bytes(n) bytes owned by the caller.
+ * mrg_grad_clip_value (gradient_clip_algorithm: value) is torch.clamp(g, -clip_value, clip_value);
+ * a NaN stays NaN.  max_norm and clip_value must be >= 0 and not NaN; n == 0 launches nothing.
+ * Either takes a buffer that is not 16-byte aligned (scalar loads instead of float4).           */
+size_t mrg_grad_clip_workspace_bytes(long n);
+int mrg_grad_clip_norm(float* grads, long n, float max_norm, float* clip_state, void* ws,
+                       hipStream_t stream);
+int mrg_grad_clip_value(float* grads, long n, float clip_value, hipStream_t stream);
+
 /* ---------------------------------------------------------------- features (data loader)
  * AudioPreprocessor (mr_gen/utils/preprocess/audio.py:6-67).  The power spectrum comes from one
  * GEMM of the frames (read in place from the waveform, row stride `hop`) with the windowed DFT

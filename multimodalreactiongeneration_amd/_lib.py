@@ -193,6 +193,9 @@ SIGNATURES = {
     "mrg_ssd_ln_cell_bwd": (c_int, [c_int, c_int, P, P, P, P, P, P, P, P, P, P, c_int, P, P, P, P]),
     "mrg_adamw_step": (c_int, [P, P, P, P, c_long, P, c_float, c_float, c_float, c_float, P, P]),
     "mrg_sgd_step": (c_int, [P, P, P, c_long, P, c_float, c_float, P, P]),
+    "mrg_grad_clip_workspace_bytes": (c_size, [c_long]),
+    "mrg_grad_clip_norm": (c_int, [P, c_long, c_float, P, P, P]),
+    "mrg_grad_clip_value": (c_int, [P, c_long, c_float, P]),
     "mrg_lstm_debug_inject": (c_int, [c_int]),
     "mrg_comm_available": (c_int, []),
     "mrg_comm_id_bytes": (c_size, []),

@@ -1800,6 +1800,50 @@ def zeros(*shape, dtype=torch.float32, device=None) -> torch.Tensor:
     return zero_(torch.empty(*shape, dtype=dtype, device=device))
 
 
+# ------------------------------------------------------------------ gradient clipping
+def _flat_f32(t: torch.Tensor, who: str):
+    _lib.require_device(t)
+    if t.dtype != torch.float32:
+        raise ValueError(f"functional.{who}: float32 required (got {t.dtype})")
+    if not t.is_contiguous():
+        raise ValueError(f"functional.{who}: contiguous tensor required (it is clipped in place, not copied)")
+
+
+def clip_grad_workspace(n: int, device) -> torch.Tensor:
+    """The per-block partials buffer mrg_grad_clip_norm needs for n elements."""
+    nbytes = _lib.load().mrg_grad_clip_workspace_bytes(int(n))
+    return torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=device)
+
+
+def clip_grad_norm_(flat_grad: torch.Tensor, max_norm: float, clip_state: Optional[torch.Tensor] = None,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_(norm_type=2, error_if_nonfinite=False) over one buffer, in place
+    (mrg_grad_clip_norm).  Returns clip_state, a device float32[2] = {norm before clipping, coefficient
+    applied}; nothing is read back.  max_norm = inf only measures.  clip_state / workspace
+    (clip_grad_workspace) may be passed in so that the call allocates nothing."""
+    _flat_f32(flat_grad, "clip_grad_norm_")
+    if clip_state is None:
+        clip_state = zeros(2, device=flat_grad.device)
+    elif not (clip_state.is_cuda and clip_state.dtype == torch.float32 and clip_state.is_contiguous()
+              and clip_state.numel() >= 2):
+        raise ValueError("functional.clip_grad_norm_: clip_state must be a contiguous device float32[2]")
+    n = flat_grad.numel()
+    if workspace is None:
+        workspace = clip_grad_workspace(n, flat_grad.device)
+        hold_scratch(workspace)
+    _lib.check(_lib.load().mrg_grad_clip_norm(_ptr(flat_grad), n, float(max_norm), _ptr(clip_state),
+                                              _ptr(workspace), _stream()), "grad clip norm")
+    return clip_state
+
+
+def clip_grad_value_(flat_grad: torch.Tensor, clip_value: float) -> torch.Tensor:
+    """torch.clamp(g, -clip_value, clip_value) in place (mrg_grad_clip_value); a NaN stays NaN."""
+    _flat_f32(flat_grad, "clip_grad_value_")
+    _lib.check(_lib.load().mrg_grad_clip_value(_ptr(flat_grad), flat_grad.numel(), float(clip_value), _stream()),
+               "grad clip value")
+    return flat_grad
+
+
 # ------------------------------------------------------------------ loss
 _LOSS_TYPES = {"huber": 0, "mse": 1, "mae": 2, "smoothl1": 3}
 

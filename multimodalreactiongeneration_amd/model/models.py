@@ -96,11 +96,14 @@ class LightningSurface(nn.Module):
                     beta=cfg.get("smoothl1_beta", 1.0))
 
     def _optimizers(self, optim):
+        # Lightning's Trainer keys, read from the optim mapping: there is no Trainer here
+        clip = dict(gradient_clip_val=optim.get("gradient_clip_val"),
+                    gradient_clip_algorithm=optim.get("gradient_clip_algorithm", "norm"))
         if optim.use_optimizer == "adam":
-            opt = FusedAdamW(self.parameters(), lr=optim.lr, weight_decay=optim.weight_decay)
+            opt = FusedAdamW(self.parameters(), lr=optim.lr, weight_decay=optim.weight_decay, **clip)
         elif optim.use_optimizer == "sgd":
             opt = FusedSGD(self.parameters(), lr=optim.lr, momentum=optim.momentum,
-                           weight_decay=optim.weight_decay)
+                           weight_decay=optim.weight_decay, **clip)
         else:
             raise ValueError("invalid optimizer type")
         self.optimizer = opt

@@ -51,6 +51,13 @@ def flatten_parameters(params, device=None):
     return flat, gflat, params
 
 
+def _check_clipping(val, algorithm):
+    if algorithm not in ("norm", "value"):
+        raise ValueError(f"gradient_clip_algorithm {algorithm!r}: 'norm' or 'value'")
+    if val is not None and not float(val) >= 0:
+        raise ValueError(f"gradient_clip_val {val!r}: None, 0 (off) or a positive number")
+
+
 class _LRGroup(dict):
     """A param group whose 'lr' assignment (LR schedulers) is mirrored to the device buffer."""
 
@@ -74,8 +81,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
     _UPDATE = ""
 
-    def __init__(self, params: Iterable, defaults):
+    def __init__(self, params: Iterable, defaults, gradient_clip_val=None, gradient_clip_algorithm="norm"):
         params = list(params)
+        _check_clipping(gradient_clip_val, gradient_clip_algorithm)   # before the parameters are re-pointed
         super().__init__(params, defaults)
         if len(self.param_groups) != 1:
             raise ValueError(f"{type(self).__name__} takes one param group (one flat buffer, one device-side LR)")
@@ -87,6 +95,56 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._lr_on_device = lr
         self._wrap_groups()
         self._err_host = self._err_event = None
+        self.clip_state = self._clip_ws = None
+        self.set_gradient_clipping(gradient_clip_val, gradient_clip_algorithm)
+
+    # ---- gradient clipping (Lightning's trainer.gradient_clip_val / gradient_clip_algorithm).  Attributes
+    # of the optimizer, as they are the Trainer's there: not a group option, not in state_dict().
+    def set_gradient_clipping(self, val, algorithm="norm"):
+        """Clip ``flat_grad`` in ``step()``, just before the update: to a total 2-norm of ``val``
+        (``"norm"``: torch.nn.utils.clip_grad_norm_) or elementwise to [-val, val] (``"value"``).  ``None`` or
+        0 switches it off; ``inf`` with ``"norm"`` only measures (``grad_norm``).  The device buffers are
+        allocated here, never in ``step()``, so call it before a step is captured into a graph."""
+        _check_clipping(val, algorithm)
+        if self.flat.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("set_gradient_clipping inside a graph capture: a captured step holds the "
+                               "launches it was recorded with; set it before graphs.capture")
+        self.gradient_clip_val = None if val is None else float(val)
+        self.gradient_clip_algorithm = algorithm
+        if self._norm_clipping():   # once allocated the buffers stay: a captured step may hold their addresses
+            if self.clip_state is None:
+                self.clip_state = torch.tensor([0.0, 1.0], dtype=torch.float32, device=self.flat.device)
+            if self._clip_ws is None and self.flat.is_cuda:
+                from . import functional as Fn
+                self._clip_ws = Fn.clip_grad_workspace(self.flat_grad.numel(), self.flat.device)
+
+    def _norm_clipping(self):
+        return bool(self.gradient_clip_val) and self.gradient_clip_algorithm == "norm"
+
+    def _clip_view(self, i, what):
+        if not self._norm_clipping():
+            raise RuntimeError(f"{what}: norm clipping is off (gradient_clip_val={self.gradient_clip_val!r}, "
+                               f"gradient_clip_algorithm={self.gradient_clip_algorithm!r})")
+        return self.clip_state[i]
+
+    @property
+    def grad_norm(self):
+        """0-d device view: the total gradient norm the last step saw, before clipping (no sync)."""
+        return self._clip_view(0, "grad_norm")
+
+    @property
+    def grad_clip_coef(self):
+        """0-d device view: the coefficient the last step multiplied the gradients by (1: not clipped)."""
+        return self._clip_view(1, "grad_clip_coef")
+
+    def _clip_gradients(self):
+        """Issued between _begin_step() and the update launch: every gradient write (side streams, the DDP
+        all-reduce) is ordered before that point already."""
+        from . import functional as Fn
+        if self.gradient_clip_algorithm == "norm":
+            Fn.clip_grad_norm_(self.flat_grad, self.gradient_clip_val, self.clip_state, self._clip_ws)
+        else:
+            Fn.clip_grad_value_(self.flat_grad, self.gradient_clip_val)
 
     def _check_group(self, group):
         pass
@@ -219,9 +277,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
 class FusedAdamW(_FlatOptimizer):
     _UPDATE = "AdamW"
 
-    def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
+                 gradient_clip_val=None, gradient_clip_algorithm="norm"):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
-                                      maximize=False, decoupled_weight_decay=True))
+                                      maximize=False, decoupled_weight_decay=True),
+                         gradient_clip_val, gradient_clip_algorithm)
         self.exp_avg = torch.zeros_like(self.flat)
         self.exp_avg_sq = torch.zeros_like(self.flat)
 
@@ -251,6 +311,8 @@ class FusedAdamW(_FlatOptimizer):
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         g = self._begin_step()
+        if self.gradient_clip_val:
+            self._clip_gradients()
         b1, b2 = g["betas"]
         _lib.check(_lib.load().mrg_adamw_step(
             _ptr(self.flat), _ptr(self.flat_grad), _ptr(self.exp_avg), _ptr(self.exp_avg_sq),
@@ -266,9 +328,10 @@ class FusedSGD(_FlatOptimizer):
     _UPDATE = "SGD"
 
     def __init__(self, params: Iterable, lr, momentum=0.0, weight_decay=0.0, dampening=0.0, nesterov=False,
-                 maximize=False):
+                 maximize=False, gradient_clip_val=None, gradient_clip_algorithm="norm"):
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
-                                      nesterov=nesterov, maximize=maximize))
+                                      nesterov=nesterov, maximize=maximize),
+                         gradient_clip_val, gradient_clip_algorithm)
         self.momentum_buf = None
         self._fit_moments(self.param_groups[0])
 
@@ -302,6 +365,8 @@ class FusedSGD(_FlatOptimizer):
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         g = self._begin_step()
+        if self.gradient_clip_val:
+            self._clip_gradients()
         _lib.check(_lib.load().mrg_sgd_step(
             _ptr(self.flat), _ptr(self.flat_grad), _ptr(self.momentum_buf), self.flat.numel(),
             _ptr(self.step_lr), float(g["weight_decay"]), float(g["momentum"]),
