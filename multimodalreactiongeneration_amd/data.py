@@ -18,7 +18,7 @@ from typing import Any, Dict, List, Sequence
 import torch
 
 from . import _lib
-from . import functional as Fn
+from .launch import _ptr, _stream
 from .features import AudioPreprocessor, MotionPreprocessorNX
 
 PADDING_VALUE = -100.0
@@ -81,8 +81,8 @@ def pad_sequences(seqs: Sequence[torch.Tensor], padding_value: float = PADDING_V
     dlens = torch.tensor(lens, dtype=torch.int32).to(dev)
     # the table and the sources are released to torch's stream-ordered caching allocator: any reuse
     # of their memory is queued behind this launch on the same stream
-    _lib.check(_lib.load().mrg_pad_sequences(B, Tmax, F, Fn._ptr(table), Fn._ptr(dlens), padding_value,
-                                             Fn._ptr(out), Fn._stream()), "pad sequences")
+    _lib.check(_lib.load().mrg_pad_sequences(B, Tmax, F, _ptr(table), _ptr(dlens), padding_value,
+                                             _ptr(out), _stream()), "pad sequences")
     if seqs[0].dim() == 1:
         out = out.view(B, Tmax)
     return out, torch.tensor(lens, dtype=torch.int64)

@@ -144,8 +144,8 @@ class GradReducer:
         self.order = []                             # bucket launch order of the last backward
         self.order_in_backward = []                 # those launched before the end-of-backward callback
         self._task = None
-        from . import functional as Fn
-        Fn.set_grad_listener(self)
+        from . import launch
+        launch.set_grad_listener(self)
 
     def touch(self):
         task = torch._C._current_graph_task_id()
@@ -177,9 +177,9 @@ class GradReducer:
                 self._launch(b)
 
     def end_of_backward(self):
-        from . import functional as Fn
+        from . import launch
         self.order_in_backward = list(self.order)
-        Fn._flush_touched()
+        launch._flush_touched()
         if self.expected is None:                    # census pass: remember the structure
             self.expected = dict(self.counts)
             missing = [n for n, p in self._named if id(p) not in self.counts]
@@ -238,9 +238,9 @@ class GradReducer:
         over the ranks on the comm stream, after the gradient buckets: the faulting rank's gradients
         are already averaged into every rank's buffer, so every rank must skip that AdamW update (the
         kernel skips on a non-zero flag) and raise, not only the rank that saw the timeout."""
-        from . import functional as Fn
+        from . import launch
         dev = self.flat_grad.device
-        err = Fn._err_flag(dev)
+        err = launch._err_flag(dev)
         if not hasattr(self, "_errf"):
             self._errf = torch.zeros(1, dtype=torch.float32, device=dev)
         cur = torch.cuda.current_stream(dev) if self.stream is not None else None
@@ -261,8 +261,8 @@ class GradReducer:
 
     def close(self):
         if self.overlap:
-            from . import functional as Fn
-            Fn.set_grad_listener(None)
+            from . import launch
+            launch.set_grad_listener(None)
 
     # ------------------------------------------------------------ after-backward mode
     def allreduce(self):

@@ -31,7 +31,9 @@ import torch
 from torch.autograd import Function
 
 from . import _lib
-from .functional import _err_flag, _gbuf, _keeps_precision, _probe, _ptr, _resln_bwd, _stream, _wgrad, _side, gemm
+from .dense import _resln_bwd
+from .gemm_ops import _wgrad, gemm
+from .launch import _err_flag, _gbuf, _keeps_precision, _probe, _ptr, _stream
 
 F32 = torch.float32
 # the forward frame loop as ONE persistent launch (ssd_loop.hip) when H = 256, HB = 64, FO <= 16,

@@ -38,8 +38,9 @@ import torch
 from torch.autograd import Function
 
 from . import _lib
-from . import functional as Fn
-from .functional import _ptr, _stream, gemm, _dx_gemm, _wt_note, _gbuf, _on_side
+from . import gemm_ops
+from .gemm_ops import _dx_gemm, _wt_note, gemm
+from .launch import _ARITH, _err_flag, _gbuf, _keeps_precision, _probe, _ptr, _stream, _ws, zeros
 from .wgrad_streams import beside_recurrence
 
 # time steps per chunk (the diagonal width); MRG_STACK_CHUNK overrides.  100 since the deferred weight
@@ -97,7 +98,7 @@ class _RingPool:
     needs its rings zero at its start; a fill per launch was one more kernel on the critical path)."""
 
     def __init__(self, n, elems, dev):
-        self.buf = Fn.zeros(max(1, n), elems, dtype=torch.int64, device=dev)
+        self.buf = zeros(max(1, n), elems, dtype=torch.int64, device=dev)
         self.next = 0
 
     def take(self, n):
@@ -112,7 +113,7 @@ def _launch_fwd(lib, items, B, Tc, H, dev, pool=None):
     """One persistent forward launch over `items` = [(chain, layer state dict, t0)]."""
     n = len(items)
     xb = pool.take(n) if pool is not None else \
-        Fn.zeros(n, lib.mrg_lstm_fwd_xbuf_bytes(B, H) // 8, dtype=torch.int64, device=dev)
+        zeros(n, lib.mrg_lstm_fwd_xbuf_bytes(B, H) // 8, dtype=torch.int64, device=dev)
     gx, gbs, gts, whh, bhh, h0, c0, y, ybs, yts, gates, cs, lay, rev = ([] for _ in range(14))
     for ch, st, t0 in items:
         r0 = t0 * B
@@ -125,11 +126,11 @@ def _launch_fwd(lib, items, B, Tc, H, dev, pool=None):
         lay += [4 * H, B * 4 * H, H, B * H, H, H, 0, 0]
         rev.append(0)
     A = lambda ct, v: (ct * n)(*v)  # noqa: E731
-    with Fn._probe("lstm_fwd", 8.0 * H * H * B * Tc * n):
+    with _probe("lstm_fwd", 8.0 * H * H * B * Tc * n):
         rc = lib.mrg_lstm_fwd(n, B, Tc, H, A(VP, gx), A(CL, gbs), A(CL, gts), A(VP, whh), A(VP, bhh),
                               A(VP, h0), A(VP, c0), A(VP, y), A(CL, ybs), A(CL, yts), A(VP, gates), A(VP, cs),
                               None, None, A(CI, rev), A(VP, [_p(xb[i]) for i in range(n)]),
-                              (CL * (8 * n))(*lay), _ptr(Fn._err_flag(dev)), _lib.cu_count(dev.index or 0), 0,
+                              (CL * (8 * n))(*lay), _ptr(_err_flag(dev)), _lib.cu_count(dev.index or 0), 0,
                               _stream())
     _lib.check(rc, "lstm fwd (encoder stack)")
 
@@ -138,7 +139,7 @@ def _launch_bwd(lib, items, B, Tc, H, dev, pool=None):
     """One persistent backward launch over `items` = [(chain, state, grads, t0, dhT, dcT, dh0, dc0)]."""
     n = len(items)
     xb = pool.take(n) if pool is not None else \
-        Fn.zeros(n, lib.mrg_lstm_bwd_xbuf_bytes(B, H) // 8, dtype=torch.int64, device=dev)
+        zeros(n, lib.mrg_lstm_bwd_xbuf_bytes(B, H) // 8, dtype=torch.int64, device=dev)
     whh, gates, cs, c0, dy, dybs, dyts, dhT, dcT, dG, dh0, dc0, lay, rev = ([] for _ in range(14))
     for ch, st, gr, t0, dh_in, dc_in, dh_out, dc_out in items:
         r0 = t0 * B
@@ -154,11 +155,11 @@ def _launch_bwd(lib, items, B, Tc, H, dev, pool=None):
     # deferred weight gradients (wgrad_streams._DEFER) run beside this recurrence, as in _LSTMFn.backward
     with beside_recurrence(dev) as cap:
         lib.mrg_lstm_set_blocks_per_cu(cap)
-        with Fn._probe("lstm_bwd", 8.0 * H * H * B * Tc * n):
+        with _probe("lstm_bwd", 8.0 * H * H * B * Tc * n):
             rc = lib.mrg_lstm_bwd(n, B, Tc, H, A(VP, whh), A(VP, gates), A(VP, cs), A(VP, c0), A(VP, dy),
                                   A(CL, dybs), A(CL, dyts), A(VP, dhT), A(VP, dcT), A(VP, dG), A(VP, dh0), A(VP, dc0),
                                   A(CI, rev), A(VP, [_p(xb[i]) for i in range(n)]), (CL * (8 * n))(*lay),
-                                  _ptr(Fn._err_flag(dev)), _lib.cu_count(dev.index or 0), 0, _stream())
+                                  _ptr(_err_flag(dev)), _lib.cu_count(dev.index or 0), 0, _stream())
         _lib.check(rc, "lstm bwd (encoder stack)")
 
 
@@ -173,15 +174,15 @@ def _arr(ct, v):
 def _bgemm(lib, M, N, K, items, lda, ldc, *, epi=0, ldaux=0, transposed=False, dev=None):
     """Same-shape products C_p = A_p w_p^T + bias_p (+ aux_p) in one launch; items = [(A ptr, w, C ptr,
     bias ptr | None, aux ptr | None)].  transposed: the products are dY w (input gradients), run as
-    dY (w^T)^T through the [in][out] copies (functional._wt); per product when a copy is missing."""
+    dY (w^T)^T through the [in][out] copies (gemm_ops._wt); per product when a copy is missing."""
     if not items:
         return
-    if Fn.planes_batched(M, N, K, items, lda, ldc, epi=epi, ldaux=ldaux, transposed=transposed):
+    if gemm_ops.planes_batched(M, N, K, items, lda, ldc, epi=epi, ldaux=ldaux, transposed=transposed):
         return
     bs = []
     for a_p, w, c_p, b_p, x_p in items:
         if transposed:
-            wt = Fn._wt(w) if M >= Fn._WT_MIN_ROWS else None
+            wt = gemm_ops._wt(w) if M >= gemm_ops._WT_MIN_ROWS else None
             if wt is None:   # no [in][out] copy: the per-product path
                 for a_p2, w2, c_p2, b_p2, x_p2 in items:
                     _dx_gemm(M, N, K, a_p2, lda, w2, c_p2, ldc, bias=b_p2, epi=epi, aux=x_p2, ldaux=ldaux, device=dev)
@@ -190,13 +191,13 @@ def _bgemm(lib, M, N, K, items, lda, ldc, *, epi=0, ldaux=0, transposed=False, d
         else:
             bs.append(_ptr(w))
     n = len(items)
-    with Fn._probe("gemm", 2.0 * M * N * K * n):
+    with _probe("gemm", 2.0 * M * N * K * n):
         rc = lib.mrg_gemm_x6g_batched(
             n, M, N, K, 1.0, _arr(VP, [it[0] for it in items]), lda, _arr(VP, bs), K, 0.0,
             _arr(VP, [it[2] for it in items]), ldc,
             None if all(it[3] is None for it in items) else _arr(VP, [it[3] for it in items]), epi,
             None if all(it[4] is None for it in items) else _arr(VP, [it[4] for it in items]), ldaux,
-            1 if Fn._ARITH[0] == "bf16" else 0, _stream())
+            1 if _ARITH[0] == "bf16" else 0, _stream())
     _lib.check(rc, "batched gemm (encoder stack)")
 
 
@@ -261,7 +262,7 @@ class _EncoderStackFn(Function):
     10 per layer]; returns the last layer's output of every chain, batch-major [B, T, H]."""
 
     @staticmethod
-    @Fn._keeps_precision
+    @_keeps_precision
     def forward(ctx, spec, *tensors):
         nls, tc, eps, sinks = spec
         ctx.sinks = sinks
@@ -348,7 +349,7 @@ class _EncoderStackFn(Function):
         return tuple(outs)
 
     @staticmethod
-    @Fn._keeps_precision
+    @_keeps_precision
     def backward(ctx, *douts):
         chains, tc, B, H = ctx.chains, ctx.tc, ctx.B, ctx.H
         lib = _lib.load()
@@ -385,7 +386,7 @@ class _EncoderStackFn(Function):
             grads.append(gl)
             if douts[m] is None:
                 douts = list(douts)
-                douts[m] = Fn.zeros(B, T, H, **f32)
+                douts[m] = zeros(B, T, H, **f32)
         douts = [d.contiguous() for d in douts]
 
         def block_off(T, c):
@@ -477,17 +478,17 @@ class _EncoderStackFn(Function):
             if gw is None:
                 gb = kw.get("gb")
                 if gb is not None:
-                    Fn.colsum(n, Nout, dY, ldy, _ptr(gb), out2=_ptr(kw.get("gb2")), device=dev)
+                    gemm_ops.colsum(n, Nout, dY, ldy, _ptr(gb), out2=_ptr(kw.get("gb2")), device=dev)
                 return
             gemm(Nout, Nin, n, dY, 1, ldy, X, 0, ldx, _ptr(gw), Nin, beta=1.0, b_hi=kw.get("x_hi", 0),
-                 b_div=kw.get("x_div", 0), splits=Fn.wgrad_splits(Nout, Nin, n), device=dev,
+                 b_div=kw.get("x_div", 0), splits=gemm_ops.wgrad_splits(Nout, Nin, n), device=dev,
                  asum_out=_ptr(kw.get("gb")), asum_out2=_ptr(kw.get("gb2")))
 
         # the partial blocks to reduce: one chunk's (starting at block bo), or every chunk's
         nb = gr["nblk"] if (t0 == 0 and t1 == T) else _ln_blocks(lib, rows, H)
 
         def ln_reduce(ws, gg, gb):
-            scratch = Fn._ws(2 * H * 4, dev).view(2, H) if (gg is None or gb is None) else None
+            scratch = _ws(2 * H * 4, dev).view(2, H) if (gg is None or gb is None) else None
             _lib.check(lib.mrg_residual_layernorm_param_reduce(
                 _ln_rows(lib, nb, H), H, _p(ws, bo * 2 * H), _ptr(gg if gg is not None else scratch[0]),
                 _ptr(gb if gb is not None else scratch[1]), 1, _stream()), "layernorm param reduce")
@@ -507,13 +508,13 @@ class _EncoderStackFn(Function):
         writes = (gw_ih, first, gbh, gw_hh, gw_ff, gb_ff, *emb, *[t for _, gg, gb in lns for t in (gg, gb)])
         if SPLIT_FORKS:   # one fork per product (the round-3 pattern, kept as a capture regression case)
             for f in parts:
-                _on_side(dev, rows, keep, f, writes=writes)
+                gemm_ops._on_side(dev, rows, keep, f, writes=writes)
             return
 
         def issue():
             for f in parts:
                 f()
-        _on_side(dev, rows, keep, issue, writes=writes)
+        gemm_ops._on_side(dev, rows, keep, issue, writes=writes)
 
     @staticmethod
     def _input_grads(chains, need):
@@ -537,7 +538,7 @@ def _ln_rows(lib, nblk, H) -> int:
 
 def stack_eligible(H, B) -> bool:
     lib = _lib.load()
-    return bool(lib.mrg_lstm_supported_hidden(H)) and H % 4 == 0 and Fn._ARITH[0] is None
+    return bool(lib.mrg_lstm_supported_hidden(H)) and H % 4 == 0 and _ARITH[0] is None
 
 
 def encoder_stack(chains: Sequence[Sequence], eps: float, chunk: int = 0) -> List[torch.Tensor]:

@@ -26,7 +26,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import functional as Fn
+from .gemm_ops import gemm
+from .launch import _ptr, _stream
 
 
 def dft_basis(nfft: int) -> torch.Tensor:
@@ -94,7 +95,7 @@ def compute_delta(x: torch.Tensor, delta_order: int) -> torch.Tensor:
                       dtype=torch.float32)
     if T <= delta_order or N == 0:
         return out  # empty, as the reference's slicing gives
-    _lib.check(_lib.load().mrg_feature_delta(N, T, C, Fn._ptr(x), C, delta_order, Fn._ptr(out), Fn._stream()),
+    _lib.check(_lib.load().mrg_feature_delta(N, T, C, _ptr(x), C, delta_order, _ptr(out), _stream()),
                "feature delta")
     return out
 
@@ -140,12 +141,12 @@ class AudioPreprocessor:
         rows = N * F
         spec = torch.empty(rows, 2 * nf, device=dev, dtype=torch.float32)
         # frame r of the batch: clip r // F, start (r % F) * shift (RowMap: ld_lo = shift, ld_hi = L)
-        Fn.gemm(rows, 2 * nf, self.nfft, Fn._ptr(x), 0, self.shift, Fn._ptr(self.basis), 1, self.nfft,
-                Fn._ptr(spec), 2 * nf, a_hi=L if N > 1 else 0, a_div=F if N > 1 else 0, device=dev)
+        gemm(rows, 2 * nf, self.nfft, _ptr(x), 0, self.shift, _ptr(self.basis), 1, self.nfft,
+                _ptr(spec), 2 * nf, a_hi=L if N > 1 else 0, a_div=F if N > 1 else 0, device=dev)
         out = torch.empty(*x.shape[:-1], F, self.nmels + 1, device=dev, dtype=torch.float32)
-        _lib.check(_lib.load().mrg_fbank_finish(rows, nf, self.nmels, Fn._ptr(spec), 2 * nf, Fn._ptr(self.melfb),
-                                                Fn._ptr(x), self.shift, self.nfft, F, L, Fn._ptr(out),
-                                                self.nmels + 1, Fn._stream()), "fbank finish")
+        _lib.check(_lib.load().mrg_fbank_finish(rows, nf, self.nmels, _ptr(spec), 2 * nf, _ptr(self.melfb),
+                                                _ptr(x), self.shift, self.nfft, F, L, _ptr(out),
+                                                self.nmels + 1, _stream()), "fbank finish")
         return out
 
     def features(self, waveform: torch.Tensor) -> torch.Tensor:

@@ -32,7 +32,7 @@ from torch import nn
 
 from . import _lib
 from . import functional as Fn
-from .functional import _ptr, _stream
+from .launch import _err_flag, _probe, _ptr, _stream, zeros
 
 F32 = torch.float32
 E_GEN, HB_GEN = 256, 64
@@ -169,33 +169,33 @@ class GenPlan:
                 w_ih, b_ih, b_hh, prev = c["lstm"]
                 if bi == 0:
                     src = msc[0] if t == 0 else ms_in
-                    with Fn._probe("gen", f_lstm + 2.0 * B * E * self.fm):
+                    with _probe("gen", f_lstm + 2.0 * B * E * self.fm):
                         _lib.check(lib.mrg_gen_lstm(B, self.fm, _ptr(src), _ptr(fe0.weight), _ptr(fe0.bias), None, None,
                                                     None, None, eps, _ptr(xb), _ptr(w_ih), _ptr(b_ih), _ptr(b_hh),
                                                     _ptr(hh), st), "gen lstm")
                 else:
-                    with Fn._probe("gen", f_lstm):
+                    with _probe("gen", f_lstm):
                         _lib.check(lib.mrg_gen_lstm(B, self.fm, None, None, None, _ptr(zf), _ptr(m3),
                                                     _ptr(prev.weight), _ptr(prev.bias), eps, _ptr(xb), _ptr(w_ih),
                                                     _ptr(b_ih), _ptr(b_hh), _ptr(hh), st), "gen lstm")
                 a, r, ga, be, w, bias = c["lin0"]
-                with Fn._probe("gen", f_lin0):
+                with _probe("gen", f_lin0):
                     _lib.check(lib.mrg_gen_linear(0, B, a, r, ga, be, E, None, None, None, eps, _ptr(y), E, w, bias,
                                                   _ptr(z), E, st), "gen mixer linear")
                 a, r, ga, be, ga2, be2, w, bias = c["lin1"]
                 a2 = _arr(_ptr(att[bi][0], t * B * E), _ptr(att[bi][1], t * B * E))
-                with Fn._probe("gen", f_lin1):
+                with _probe("gen", f_lin1):
                     _lib.check(lib.mrg_gen_linear(1, B, a, r, ga, be, E, a2, ga2, be2, eps, _ptr(y01), 2 * E, w,
                                                   bias, _ptr(z01), 2 * E, st), "gen integrators")
                 a, r, ga, be, w, bias = c["lin2"]
-                with Fn._probe("gen", f_lin2):
+                with _probe("gen", f_lin2):
                     _lib.check(lib.mrg_gen_linear(2, B, a, r, ga, be, 2 * E, None, None, None, eps, None, 0, w, bias,
                                                   _ptr(m3), E, st), "gen cat_linear")
                 w1, b1, w2, b2 = c["ffn"]
-                with Fn._probe("gen", f_ffn):
+                with _probe("gen", f_ffn):
                     _lib.check(lib.mrg_gen_ffn(B, E, _ptr(m3), None, None, None, eps, _ptr(w1), _ptr(b1), _ptr(w2),
                                                _ptr(b2), _ptr(zf), None, 0, None, None, None, t, st), "gen ffn")
-            with Fn._probe("gen", f_out):
+            with _probe("gen", f_out):
                 _lib.check(lib.mrg_gen_ffn(B, self.fm, _ptr(zf), _ptr(m3), _ptr(lastln.weight), _ptr(lastln.bias),
                                            eps, _ptr(ow1), _ptr(ob1), _ptr(ow2), _ptr(ob2), None, _ptr(pred),
                                            T * self.fm, _ptr(ms_in), _ptr(msc[t]), _ptr(mask_u8), t, st),
@@ -217,13 +217,13 @@ class GenPlan:
         ow1, ob1, ow2, ob2, _ = self.out
         fe0 = self.fe[0]
         ptrs += [fe0.weight, fe0.bias, ow1, ob1, ow2, ob2]
-        ring = Fn.zeros(max(1, lib.mrg_gen_loop_ring_bytes(B) // 8), dtype=torch.int64, device=msc.device)
+        ring = zeros(max(1, lib.mrg_gen_loop_ring_bytes(B) // 8), dtype=torch.int64, device=msc.device)
         E = E_GEN
         flop = T * (len(self.blocks) * 2.0 * B * (4 * E * E + E * E + 2 * E * E + 2 * E * E + 2 * HB_GEN * E)
                     + 2.0 * B * HB_GEN * (E + self.fm))
-        with Fn._probe("gen", flop):
+        with _probe("gen", flop):
             _lib.check(lib.mrg_gen_loop(B, T, self.fm, len(self.blocks), self.eps, _arr(*ptrs), len(ptrs), _ptr(msc),
-                                        _ptr(mask_u8), _ptr(pred), _ptr(ring), _ptr(Fn._err_flag(msc.device)), st),
+                                        _ptr(mask_u8), _ptr(pred), _ptr(ring), _ptr(_err_flag(msc.device)), st),
                        "gen loop")
         return pred
 

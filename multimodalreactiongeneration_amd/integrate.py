@@ -30,8 +30,10 @@ import torch
 from torch.autograd import Function
 
 from . import _lib
-from . import functional as Fn
-from .functional import _ptr, _stream, gemm, _dx_gemm, _wt_note, _gbuf, _on_side
+from . import gemm_ops
+from .attention import visible_pairs
+from .gemm_ops import _dx_gemm, _wt_note, gemm
+from .launch import _ARITH, _gbuf, _keeps_precision, _probe, _ptr, _stream, _ws
 
 VP, CL, CI = ctypes.c_void_p, ctypes.c_long, ctypes.c_int
 _PER = 10   # in_w, in_b, out_w, out_b, ln1 w, ln1 b, ff w, ff b, ln2 w, ln2 b
@@ -47,27 +49,27 @@ def _p(t, off=0):
 
 def _bgemm(M, N, K, items, lda, ldc, *, epi=0, ldaux=0, transposed=False, beta=0.0, dev=None):
     """Same-shape products in one launch: items = [(A ptr, w, C ptr, bias ptr | None, aux ptr | None)];
-    transposed: input-gradient products dY w through w's [in][out] copy (functional._wt), one by one
+    transposed: input-gradient products dY w through w's [in][out] copy (gemm_ops._wt), one by one
     when a copy is missing."""
     lib = _lib.load()
-    if Fn.planes_batched(M, N, K, items, lda, ldc, epi=epi, ldaux=ldaux, beta=beta, transposed=transposed):
+    if gemm_ops.planes_batched(M, N, K, items, lda, ldc, epi=epi, ldaux=ldaux, beta=beta, transposed=transposed):
         return
     bs = []
     for a_p, w, c_p, b_p, x_p in items:
-        wt = Fn._wt(w) if (transposed and M >= Fn._WT_MIN_ROWS) else (None if transposed else w)
+        wt = gemm_ops._wt(w) if (transposed and M >= gemm_ops._WT_MIN_ROWS) else (None if transposed else w)
         if wt is None:
             for a2, w2, c2, b2, x2 in items:
                 _dx_gemm(M, N, K, a2, lda, w2, c2, ldc, bias=b2, epi=epi, aux=x2, ldaux=ldaux, beta=beta, device=dev)
             return
         bs.append(_ptr(wt))
     n = len(items)
-    with Fn._probe("gemm", 2.0 * M * N * K * n):
+    with _probe("gemm", 2.0 * M * N * K * n):
         rc = lib.mrg_gemm_x6g_batched(
             n, M, N, K, 1.0, _arr(VP, [it[0] for it in items]), lda, _arr(VP, bs), K, beta,
             _arr(VP, [it[2] for it in items]), ldc,
             None if all(it[3] is None for it in items) else _arr(VP, [it[3] for it in items]), epi,
             None if all(it[4] is None for it in items) else _arr(VP, [it[4] for it in items]), ldaux,
-            1 if Fn._ARITH[0] == "bf16" else 0, _stream())
+            1 if _ARITH[0] == "bf16" else 0, _stream())
     _lib.check(rc, "batched gemm (integrator)")
 
 
@@ -115,7 +117,7 @@ class _IntegrateFn(Function):
     kpad_0..kpad_{n-1}, 10 per integrator, cat_w, cat_b (pads: uint8 [B, T] flags or None)."""
 
     @staticmethod
-    @Fn._keeps_precision
+    @_keeps_precision
     def forward(ctx, spec, *t):
         n, heads, causal, eps = spec
         q_in = t[0]
@@ -150,7 +152,7 @@ class _IntegrateFn(Function):
         scale = 1.0 / math.sqrt(D)
         for i in range(n):
             Tk = kv2[i].shape[1]
-            with Fn._probe("attn_fwd", 4.0 * D * B * heads * Fn.visible_pairs(Tq, Tk, causal)):
+            with _probe("attn_fwd", 4.0 * D * B * heads * visible_pairs(Tq, Tk, causal)):
                 rc = lib.mrg_attention_fwd(B, heads, Tq, Tk, D, _ptr(Q[i]), Tq * E, E, _ptr(KV[i]), Tk * 2 * E,
                                            2 * E, _p(KV[i], E), Tk * 2 * E, 2 * E, _ptr(O[i]), Tq * E, E,
                                            _ptr(lse[i]), _ptr(qpads[i]), _ptr(kpads[i]), int(causal), scale, _stream())
@@ -182,7 +184,7 @@ class _IntegrateFn(Function):
         return out
 
     @staticmethod
-    @Fn._keeps_precision
+    @_keeps_precision
     def backward(ctx, dout):
         n, heads, causal, scale = ctx.spec
         s = ctx.saved_tensors
@@ -217,8 +219,8 @@ class _IntegrateFn(Function):
         dKV = [torch.empty(B, kv.shape[1], 2 * E, **f32) for kv in kv2]
         for i in range(n):
             Tk = kv2[i].shape[1]
-            ws = Fn._ws(lib.mrg_attention_bwd_workspace_bytes(B, heads, Tq), dev)
-            with Fn._probe("attn_bwd", 10.0 * D * B * heads * Fn.visible_pairs(Tq, Tk, causal)):
+            ws = _ws(lib.mrg_attention_bwd_workspace_bytes(B, heads, Tq), dev)
+            with _probe("attn_bwd", 10.0 * D * B * heads * visible_pairs(Tq, Tk, causal)):
                 rc = lib.mrg_attention_bwd(
                     B, heads, Tq, Tk, D, _ptr(Q[i]), Tq * E, E, _ptr(KV[i]), Tk * 2 * E, 2 * E, _p(KV[i], E),
                     Tk * 2 * E, 2 * E, _ptr(O[i]), Tq * E, E, _ptr(lse[i]), _ptr(qpads[i]), _ptr(kpads[i]), int(causal),
@@ -269,15 +271,15 @@ class _IntegrateFn(Function):
         def wg(dY, ldy, X, ldx, rows, Nout, Nin, gw, gb=None):
             if gw is None:
                 if gb is not None:
-                    Fn.colsum(rows, Nout, dY, ldy, _ptr(gb), device=dev)
+                    gemm_ops.colsum(rows, Nout, dY, ldy, _ptr(gb), device=dev)
                 return
             gemm(Nout, Nin, rows, dY, 1, ldy, X, 0, ldx, _ptr(gw), Nin, beta=1.0,
-                 splits=Fn.wgrad_splits(Nout, Nin, rows), device=dev, asum_out=_ptr(gb))
+                 splits=gemm_ops.wgrad_splits(Nout, Nin, rows), device=dev, asum_out=_ptr(gb))
 
         def reduce(ws, gg, gb):
             if gg is None and gb is None:
                 return
-            scratch = Fn._ws(2 * E * 4, dev).view(2, E) if (gg is None or gb is None) else None
+            scratch = _ws(2 * E * 4, dev).view(2, E) if (gg is None or gb is None) else None
             _lib.check(lib.mrg_residual_layernorm_param_reduce(
                 N, E, _ptr(ws), _ptr(gg if gg is not None else scratch[0]), _ptr(gb if gb is not None else scratch[1]),
                 1, _stream()), "layernorm param reduce")
@@ -294,7 +296,7 @@ class _IntegrateFn(Function):
                 Nk = kv2[i].shape[0] * kv2[i].shape[1]
                 wg(_ptr(dKV[i]), 2 * E, _ptr(kv2[i]), E, Nk, 2 * E, E, None if g["in_w"] is None else g["in_w"][E:],
                    None if g["in_b"] is None else g["in_b"][E:])
-        _on_side(dev, N, keep, issue, writes=(gcw, gcb, *[t for g in per for t in g.values()]))
+        gemm_ops._on_side(dev, N, keep, issue, writes=(gcw, gcb, *[t for g in per for t in g.values()]))
 
 
 def _bln_fwd(rows, E, eps, items):

@@ -33,6 +33,7 @@ import torch
 from torch import nn
 
 from .. import functional as Fn
+from ..launch import _ARITH
 from ..configs import as_attr
 from ..metrics import MultiTargetMetrics
 from ..optim import FusedAdamW, FusedSGD
@@ -503,7 +504,7 @@ class LSTMwithSample(LightningSurface):
                 sampling_mask = (torch.ones if full_generation else torch.zeros)(T, dtype=torch.bool)
         # the fused decode computes in fp32 only: under precision='bf16' the per-frame path runs, so
         # every product of the step follows the selected arithmetic (as _LSTMCellFn's fused step does)
-        if self.use_fused_decode and Fn._ARITH[0] is None and self._fused_params() is not None:
+        if self.use_fused_decode and _ARITH[0] is None and self._fused_params() is not None:
             return self._fused_prediction(batch, sampling_mask), target
         # time-major copies made once: every per-frame slice below is then contiguous, so the
         # ops of the T single-frame forwards run on it in place (no per-frame layout copies)

@@ -29,7 +29,7 @@ from typing import Iterable
 import torch
 
 from . import _lib
-from .functional import _ptr, _stream, _err_flag
+from .launch import _err_flag, _ptr, _stream
 
 
 def flatten_parameters(params, device=None):

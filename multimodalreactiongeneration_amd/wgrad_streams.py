@@ -1,10 +1,10 @@
 """Where each weight-gradient product runs: on the current stream, forked to the side stream, or
 queued and issued beside the next backward recurrence on a third stream."""
-# The autograd ops (functional.py, encoder_stack.py, integrate.py) hand every parameter-gradient launch
+# The autograd ops (gemm_ops._on_side for dense.py, recurrent.py, encoder_stack.py, integrate.py) hand every parameter-gradient launch
 # to on_side / side and bracket their backward recurrences with beside_recurrence; the streams, the
 # waits, the captured graph's fork points and the end-of-backward join are decided here.  Nothing is
-# imported from functional: a queued item's compute precision travels inside the callable handed in,
-# and functional.set_grad_listener says whether deferral is allowed (allow_defer).
+# imported from the op modules: a queued item's compute precision travels inside the callable handed in,
+# and launch.set_grad_listener says whether deferral is allowed (allow_defer).
 import collections
 import contextlib
 import ctypes
@@ -42,7 +42,7 @@ _SIDE_MIN_ROWS = 2048
 # current stream (fewer than _SIDE_MIN_ROWS rows) first flushes the queue.  Not used while a
 # gradient-ready listener (DDP bucket overlap) needs each write issued when it is reported.
 _DEFER = [os.environ.get("MRG_WGRAD_DEFER", "1") == "1"]
-_DEFER_ALLOWED = [True]   # False while a gradient-ready listener is set (functional.set_grad_listener)
+_DEFER_ALLOWED = [True]   # False while a gradient-ready listener is set (launch.set_grad_listener)
 # The queue flushed beside the recurrences runs on a stream of its own (the recurrence stream), the rest
 # of the side work (the end-of-backward flush: the products of the layers below the last recurrence) on
 # the side stream, so

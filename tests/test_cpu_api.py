@@ -1,5 +1,6 @@
 """CPU-only checks: the C-ABI library loads and exports what include/mrg.h declares; the
 drop-in API matches the reference's module tree; the product path refuses CPU tensors."""
+import ast
 import os
 import re
 
@@ -256,3 +257,63 @@ def test_side_stream_flush_conflicts():
     assert not Fn._conflicts([(None, (), None, Fn._writes((b, None)))], rec)   # a different buffer
     assert Fn._conflicts([(None, (), None, None)], rec)                       # unknown writes
     assert Fn._conflicts([(None, (), None, Fn._writes((b,)))], None)          # recurrence stream unknown
+
+
+# ------------------------------------------------------------------ functional.py is a facade over layered modules
+PKG = "multimodalreactiongeneration_amd"
+LAYERS = (("launch",), ("gemm_ops",), ("dense", "recurrent", "attention", "losses"))   # import order, top first
+ALIASES = {"_side": "side"}   # functional's name -> the owner's name, where they differ
+
+
+def _package_imports(name):
+    """The package's own modules that module ``name`` imports (``from . import x``, ``from .x import y``)."""
+    out = set()
+    for node in ast.walk(_module_ast(name)):
+        if isinstance(node, ast.ImportFrom) and (node.level or (node.module or "").startswith(PKG)):
+            mod = (node.module or "").replace(PKG, "").strip(".")
+            out.update([mod.split(".")[0]] if mod else [a.name for a in node.names])
+        elif isinstance(node, ast.Import):
+            out.update(a.name[len(PKG) + 1:].split(".")[0] for a in node.names if a.name.startswith(PKG + "."))
+    return out
+
+
+def _module_ast(name):
+    return ast.parse(open(os.path.join(ROOT, PKG, name + ".py")).read())
+
+
+def test_functional_is_a_facade_with_every_earlier_name():
+    """Every name functional had before it was split (tests/golden/functional_names.txt: its module
+    namespace then, without imported modules, typing names, torch's Function and the unused F32) is
+    still there and IS the object of that name in the module that owns it; the file only imports."""
+    import importlib
+    fn = importlib.import_module(PKG + ".functional")
+    owners = [importlib.import_module(f"{PKG}.{m}") for layer in LAYERS for m in layer]
+    owners.append(importlib.import_module(PKG + ".wgrad_streams"))
+    names = open(os.path.join(ROOT, "tests", "golden", "functional_names.txt")).read().split()
+    assert len(names) > 100
+    for n in names:
+        assert hasattr(fn, n), f"functional.{n} is gone"
+        own = ALIASES.get(n, n)
+        holders = [m for m in owners if own in vars(m)]   # the owner, and layers below it that import the name
+        assert holders, f"no layered module holds {own}"
+        assert all(getattr(fn, n) is vars(m)[own] for m in holders), f"functional.{n} is not its owner's object"
+    body = _module_ast("functional").body
+    assert isinstance(body[0], ast.Expr) and isinstance(getattr(body[0].value, "value", None), str)
+    assert all(isinstance(node, (ast.Import, ast.ImportFrom)) for node in body[1:]), "functional.py defines something"
+
+
+def test_functional_modules_import_only_upward():
+    """launch < gemm_ops < the op families: a module imports from earlier layers only (and recurrent and
+    attention from dense, for the residual LayerNorm), from _lib, rng and wgrad_streams, never from
+    functional; wgrad_streams and _lib import none of them."""
+    allowed = {"_lib", "wgrad_streams", "rng"}
+    same_layer = {"recurrent": {"dense"}, "attention": {"dense"}}
+    for layer in LAYERS:
+        for mod in layer:
+            got = _package_imports(mod)
+            assert "functional" not in got, mod
+            assert got <= allowed | same_layer.get(mod, set()), f"{mod} imports {sorted(got - allowed)}"
+        allowed |= set(layer)
+    layered = {m for layer in LAYERS for m in layer} | {"functional"}
+    for mod in ("wgrad_streams", "_lib", "rng"):
+        assert not _package_imports(mod) & layered, mod

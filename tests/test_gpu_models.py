@@ -607,14 +607,14 @@ def test_fused_integrator_matches_module_path(ratio, B, T):
 
 def _tapped(fn):
     """Run fn() with the FFN ReLU tap on: (fn's result, {Linear prefix: bool mask on the CPU})."""
-    from multimodalreactiongeneration_amd import functional as Fn
-    Fn.RELU_TAP = {}
+    from multimodalreactiongeneration_amd import dense   # _tap_relu reads RELU_TAP there
+    dense.RELU_TAP = {}
     try:
         r = fn()
         torch.cuda.synchronize()
-        tap = Fn.RELU_TAP
+        tap = dense.RELU_TAP
     finally:
-        Fn.RELU_TAP = None
+        dense.RELU_TAP = None
     return r, tap
 
 

@@ -356,13 +356,15 @@ def test_weight_grad_with_fused_bias_sums(rows, N, In, splits, time_shift, gemm_
         dy_ptr, x_ptr = Fn._ptr(dYd), Fn._ptr(Xd)
     gw0, gb0 = torch.randn(N, In, generator=g), torch.randn(N, generator=g)
     gw, gb, gb2 = gw0.to(DEV), gb0.to(DEV), gb0.to(DEV) * 2
-    orig = Fn.wgrad_splits
-    Fn.wgrad_splits = lambda *a: splits
+    from multimodalreactiongeneration_amd import gemm_ops   # _wgrad reads wgrad_splits there
+    orig, asked = gemm_ops.wgrad_splits, []
+    gemm_ops.wgrad_splits = lambda *a: asked.append(a) or splits
     try:
         Fn._wgrad(dy_ptr, N, x_ptr, In, dY.shape[0], N, In, gw, torch.device(DEV), gb=gb, gb2=gb2, **kw)
     finally:
-        Fn.wgrad_splits = orig
+        gemm_ops.wgrad_splits = orig
     torch.cuda.synchronize()
+    assert asked == [(N, In, dY.shape[0])], "the product did not run with the forced split count"
     ref_w = gw0.double() + dY.double().t() @ X.double()
     ref_b = gb0.double() + dY.double().sum(0)
     assert rel_err(gw, ref_w) < TOL

@@ -59,10 +59,9 @@ def run(names):
                 setattr(lib, sym, (lambda *a, busy=busy: busy(1, 64, 256, 0.5, a[-1])) if tiny else _noop)
     side_saved = None
     if "SIDE" in names:
-        import multimodalreactiongeneration_amd.encoder_stack as ES
-        import multimodalreactiongeneration_amd.integrate as IG
-        side_saved = (Fn._on_side, ES._on_side, IG._on_side)
-        Fn._on_side = ES._on_side = IG._on_side = lambda device, rows, keep, fn, writes=None: None
+        from multimodalreactiongeneration_amd import gemm_ops   # every caller resolves _on_side there
+        side_saved = gemm_ops._on_side
+        gemm_ops._on_side = lambda device, rows, keep, fn, writes=None: None
     try:
         dev = torch.device("cuda", 0)
         mc, oc, me = C.lstmformer_config(ratio=1)
@@ -89,9 +88,7 @@ def run(names):
         for sym, f in saved.items():
             setattr(lib, sym, f)
         if side_saved is not None:
-            import multimodalreactiongeneration_amd.encoder_stack as ES
-            import multimodalreactiongeneration_amd.integrate as IG
-            Fn._on_side, ES._on_side, IG._on_side = side_saved
+            gemm_ops._on_side = side_saved
         Fn._ERR.clear()
 
 

@@ -10,7 +10,7 @@ import traceback
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # repo root
-from multimodalreactiongeneration_amd import configs as C, functional as Fn, wgrad_streams as WS  # noqa: E402
+from multimodalreactiongeneration_amd import configs as C, gemm_ops, wgrad_streams as WS  # noqa: E402
 from multimodalreactiongeneration_amd.model import Metaformer  # noqa: E402
 from multimodalreactiongeneration_amd.synthetic import make_batch  # noqa: E402
 
@@ -31,7 +31,7 @@ def main():
     model = Metaformer(mc, oc, me).to(dev)
     batch = make_batch(B=64, T=300, seed=1234, device=dev)
     log = []
-    orig_on_side, orig_flush, orig_bracket = Fn._on_side, WS._flush_deferred, WS.beside_recurrence
+    orig_on_side, orig_flush, orig_bracket = gemm_ops._on_side, WS._flush_deferred, WS.beside_recurrence
 
     def on_side(device, rows, keep, fn, writes=None):
         log.append(f"queue  rows={rows} defer={WS._defers(device, rows)} from {where()}")
@@ -45,12 +45,9 @@ def main():
     def bracket(device):
         log.append(f"recurrence pending={len(WS._STATES[torch.device(device).index or 0].pending)} from {where()}")
         return orig_bracket(device)
-    Fn._on_side, WS._flush_deferred = on_side, flush
-    from multimodalreactiongeneration_amd import encoder_stack, integrate
-    for mod in (encoder_stack, integrate):
-        if hasattr(mod, "_on_side"):
-            mod._on_side = on_side
-    for mod in (Fn, encoder_stack):
+    gemm_ops._on_side, WS._flush_deferred = on_side, flush   # every caller resolves _on_side in gemm_ops
+    from multimodalreactiongeneration_amd import encoder_stack, recurrent
+    for mod in (recurrent, encoder_stack):
         mod.beside_recurrence = bracket
     for it in range(2):
         log.clear()

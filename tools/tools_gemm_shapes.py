@@ -49,10 +49,15 @@ def census(step):
         e1.record()
         rec.append(((M, N, K, transA, transB, kw.get("splits", 1), kw.get("asum_out") is not None), e0, e1))
 
-    Fn.gemm = timed_gemm
+    # every module of the package that imported gemm by name resolves it in its own namespace
+    holders = [m for n, m in list(sys.modules.items())
+               if n.startswith("multimodalreactiongeneration_amd") and getattr(m, "gemm", None) is orig]
+    for m in holders:
+        m.gemm = timed_gemm
     step()
     torch.cuda.synchronize()
-    Fn.gemm = orig
+    for m in holders:
+        m.gemm = orig
     agg = collections.defaultdict(lambda: [0, 0.0])
     for key, e0, e1 in rec:
         a = agg[key]
