@@ -34,8 +34,10 @@ from . import _lib
 from .dense import _resln_bwd
 from .gemm_ops import _wgrad, gemm
 from .launch import _err_flag, _gbuf, _keeps_precision, _probe, _ptr, _stream
+from .model.forms import LstmLn
 
 F32 = torch.float32
+_PER = len(LstmLn._fields)
 # the forward frame loop as ONE persistent launch (ssd_loop.hip) when H = 256, HB = 64, FO <= 16,
 # nl <= 4 and its grid fits; MRG_SSD_LOOP=0 keeps the L + 1 launches per frame
 _LOOP = [os.environ.get("MRG_SSD_LOOP", "1") == "1"]
@@ -55,7 +57,7 @@ class _SSDecodeFn(Function):
 
     tensors: a_s [B, T, SA] sampler outputs of the frames, mp [B, T, FMp] partner motion,
     ms [B, T, FM] teacher self motion, mask [T] (device uint8), w_f [H, SA+FMp+FM], b_f [H],
-    then per layer (w_ih [4H, H], w_hh, b_ih, b_hh, ln_w, ln_b), then w1 [HB, H], b1, w2 [FO, HB], b2.
+    then per layer forms.LstmLn's fields (w_ih [4H, H], ...), then w1 [HB, H], b1, w2 [FO, HB], b2.
     """
 
     @staticmethod
@@ -70,8 +72,8 @@ class _SSDecodeFn(Function):
         H, F = w_f.shape
         if F != SA + FMp + FM:
             raise RuntimeError(f"feature_projection [{H}, {F}] vs inputs {SA} + {FMp} + {FM}")
-        layers = [params[6 * i:6 * i + 6] for i in range(nl)]
-        w1, b1, w2, b2 = params[6 * nl:6 * nl + 4]
+        layers = [LstmLn._make(params[_PER * i:_PER * (i + 1)]) for i in range(nl)]
+        w1, b1, w2, b2 = params[_PER * nl:_PER * nl + 4]
         HB, FO = w1.shape[0], w2.shape[0]
         if FO != FM:
             raise RuntimeError("the prediction feeds back as motion_self: output size must equal its features")
@@ -100,14 +102,14 @@ class _SSDecodeFn(Function):
         y = torch.empty(B, T, FO, device=dev, dtype=F32)
         msc = ms.contiguous()
         slab, gslab, zslab = B * H, B * 4 * H, B * HB
-        lw, lb = layers[-1][4], layers[-1][5]
+        lw, lb = layers[-1].ln_w, layers[-1].ln_b
         if _LOOP[0] and H == 256 and HB == 64 and FO <= 16 and nl <= 4 and lib.mrg_ssd_loop_fits(B, 0) == 1:
             # the loop stores the gates, c, h and X_0; the LayerNorm outputs (X_i, U) and statistics,
             # Z, y and X_f's ms columns are formed after it (below): stored inside the loop they fell on
             # one member, which then ran ~1.2 us behind its group at every stage (ssd_loop.hip)
             lp = []
-            for i, (w_ih, _w_hh, b_ih, b_hh, g_, b_) in enumerate(layers):
-                lp += [w_ih, b_ih, b_hh, g_, b_, X[i] if i == 0 else None, G[i], C[i], Hs[i]]
+            for i, lay in enumerate(layers):
+                lp += [lay.w_ih, lay.b_ih, lay.b_hh, lay.ln_w, lay.ln_b, X[i] if i == 0 else None, G[i], C[i], Hs[i]]
             lpa = (ctypes.c_void_p * len(lp))(*[_ptr(q) for q in lp])
             ring = torch.zeros(max(1, lib.mrg_ssd_loop_ring_bytes(B, nl) // 8), dtype=torch.int64, device=dev)
             # algorithmic FLOPs (bench's "ssd" family): gates 8H^2 per row and layer, FFN, the ms columns
@@ -118,12 +120,12 @@ class _SSDecodeFn(Function):
                     _ptr(b2), _ptr(msc), msc.stride(0), msc.stride(1), _ptr(mask), _ptr(ring),
                     _ptr(_err_flag(dev)), _stream()), "ssd loop fwd")
             rows = T * B
-            for i, (_w_ih, _w_hh, _b_ih, _b_hh, g_, b_) in enumerate(layers):
+            for i, lay in enumerate(layers):
                 # X_{i+1} (U after the last layer) = LN(h_i + X_i) with its statistics
                 out = X[i + 1] if i + 1 < nl else U
-                _lib.check(lib.mrg_residual_layernorm_fwd(rows, H, _ptr(Hs[i]), _ptr(X[i]), _ptr(g_), _ptr(b_), eps,
-                                                          _ptr(out), _ptr(stats[i][0]), _ptr(stats[i][1]),
-                                                          _stream()), "ssd layernorm")
+                _lib.check(lib.mrg_residual_layernorm_fwd(rows, H, _ptr(Hs[i]), _ptr(X[i]), _ptr(lay.ln_w),
+                                                          _ptr(lay.ln_b), eps, _ptr(out), _ptr(stats[i][0]),
+                                                          _ptr(stats[i][1]), _stream()), "ssd layernorm")
             gemm(rows, HB, H, _ptr(U), 0, H, _ptr(w1), 1, H, _ptr(Z), HB, bias=_ptr(b1), epi=1, device=dev)
             y_tb = torch.empty(T, B, FO, device=dev, dtype=F32)
             gemm(rows, FO, HB, _ptr(Z), 0, HB, _ptr(w2), 1, HB, _ptr(y_tb), FO, bias=_ptr(b2), device=dev)
@@ -137,8 +139,8 @@ class _SSDecodeFn(Function):
         else:
             T_launch = T
         for t in range(T_launch):
-            for i, (w_ih, _w_hh, b_ih, b_hh, _g, _b) in enumerate(layers):
-                cell = (_ptr(w_ih), _ptr(b_ih), _ptr(b_hh), _ptr(G[i], t * gslab), _ptr(C[i], t * slab),
+            for i, lay in enumerate(layers):
+                cell = (_ptr(lay.w_ih), _ptr(lay.b_ih), _ptr(lay.b_hh), _ptr(G[i], t * gslab), _ptr(C[i], t * slab),
                         _ptr(Hs[i], t * slab), _stream())
                 if i == 0:
                     # X = P(t) + ms_in(t) W_ms^T, ms_in(t) = mask[t-1] ? y(t-1) : ms[t-1] (y(t-1) from z(t-1))
@@ -148,7 +150,7 @@ class _SSDecodeFn(Function):
                         _ptr(y, (t - 1) * FO) if t else None, T * FO, _ptr(xf, t * B * F + SA + FMp),
                         _ptr(X[0], t * slab), *cell), "ssd feat/gate/cell fwd")
                 else:
-                    pw, pb = layers[i - 1][4], layers[i - 1][5]
+                    pw, pb = layers[i - 1].ln_w, layers[i - 1].ln_b
                     _lib.check(lib.mrg_ssd_gate_cell_fwd(
                         B, H, 1, None, _ptr(Hs[i - 1], t * slab), _ptr(X[i - 1], t * slab), _ptr(pw), _ptr(pb), eps,
                         _ptr(X[i], t * slab), _ptr(stats[i - 1][0], t * B), _ptr(stats[i - 1][1], t * B), *cell),
@@ -171,10 +173,10 @@ class _SSDecodeFn(Function):
         nl, eps, B, T, SA, FMp, FM, H, F, HB, FO = ctx.spec
         sv = ctx.saved_tensors
         mask, w_f, b_f = sv[:3]
-        params = sv[3:3 + 6 * nl + 4]
-        layers = [params[6 * i:6 * i + 6] for i in range(nl)]
-        w1, b1, w2, b2 = params[6 * nl:6 * nl + 4]
-        rest = sv[3 + 6 * nl + 4:]
+        params = sv[3:3 + _PER * nl + 4]
+        layers = [LstmLn._make(params[_PER * i:_PER * (i + 1)]) for i in range(nl)]
+        w1, b1, w2, b2 = params[_PER * nl:_PER * nl + 4]
+        rest = sv[3 + _PER * nl + 4:]
         xf, U, Z, wms_t = rest[:4]
         X, G, C, Hs, stats = (list(rest[4 + k * nl:4 + (k + 1) * nl]) for k in range(5))
         dev = xf.device
@@ -193,9 +195,9 @@ class _SSDecodeFn(Function):
         ext = nl >= 2
         loop = _bwd_loop(lib, B, H, HB, FO, nl)
         # W_ih^T copies: the per-frame dX = dG W_ih reads both operands k-contiguous (float4)
-        w_t = [None if (loop or (ext and i == 0)) else lay[0].t().contiguous() for i, lay in enumerate(layers)]
+        w_t = [None if (loop or (ext and i == 0)) else lay.w_ih.t().contiguous() for i, lay in enumerate(layers)]
         # v = [W1 gamma | W1 beta] [HB, 2] of the last LayerNorm: its row sums through W1 (decode.hip)
-        lw, lb = layers[-1][4], layers[-1][5]
+        lw, lb = layers[-1].ln_w, layers[-1].ln_b
         gb = torch.stack([lw.detach(), lb.detach()])
         v = torch.empty(HB, 2, device=dev, dtype=F32)
         gemm(HB, 2, H, _ptr(w1), 0, H, _ptr(gb), 1, H, _ptr(v), 2, device=dev)
@@ -203,12 +205,12 @@ class _SSDecodeFn(Function):
         # with vt = W_ms^T W_ih0), so its dX (dfeat) is one GEMM over all frames after the loop
         if ext:
             vt = torch.empty(FM, 4 * H, device=dev, dtype=F32)
-            gemm(FM, 4 * H, H, _ptr(wms_t), 0, H, _ptr(layers[0][0]), 1, H, _ptr(vt), 4 * H, device=dev)
+            gemm(FM, 4 * H, H, _ptr(wms_t), 0, H, _ptr(layers[0].w_ih), 1, H, _ptr(vt), 4 * H, device=dev)
             dyx = None if loop else torch.empty(T, B, FM, device=dev, dtype=F32)
         if loop:
             lp = []
             for i, lay in enumerate(layers):
-                lp += [lay[0] if i else None, lay[4], lay[5], X[i], G[i], C[i], Hs[i], stats[i][0], stats[i][1],
+                lp += [lay.w_ih if i else None, lay.ln_w, lay.ln_b, X[i], G[i], C[i], Hs[i], stats[i][0], stats[i][1],
                        gs[i], dG[i], dX[i] if i else None]
             lpa = (ctypes.c_void_p * len(lp))(*[_ptr(q) for q in lp])
             ring = torch.zeros(max(1, lib.mrg_ssd_loop_bwd_ring_bytes(B) // 8), dtype=torch.int64, device=dev)
@@ -236,7 +238,7 @@ class _SSDecodeFn(Function):
                     bottom = ext and i == 0
                     _lib.check(lib.mrg_ssd_ln_cell_bwd(
                         B, H, _ptr(dX[i + 1], t * slab), _ptr(Hs[i], t * slab), _ptr(X[i], t * slab),
-                        _ptr(layers[i][4]), _ptr(stats[i][0], t * B), _ptr(stats[i][1], t * B), *cell, FM,
+                        _ptr(layers[i].ln_w), _ptr(stats[i][0], t * B), _ptr(stats[i][1], t * B), *cell, FM,
                         _ptr(vt) if bottom else None, _ptr(wms_t) if bottom else None,
                         _ptr(dyx, t * B * FM) if bottom else None, _stream()), "ssd ln/cell bwd")
                     if bottom:
@@ -245,7 +247,7 @@ class _SSDecodeFn(Function):
                 _lib.check(lib.mrg_ssd_dx(B, H, _ptr(dG[i], t * gslab), _ptr(w_t[i]), _ptr(gs[i], t * slab),
                                           _ptr(dX[i], t * slab), _stream()), "ssd dx")
         if ext:  # every frame's dfeat = dG0 W_ih0 + g0 in one GEMM
-            gemm(T * B, H, 4 * H, _ptr(dG[0]), 0, 4 * H, _ptr(layers[0][0]), 0, H, _ptr(dX[0]), H, epi=3,
+            gemm(T * B, H, 4 * H, _ptr(dG[0]), 0, 4 * H, _ptr(layers[0].w_ih), 0, H, _ptr(dX[0]), H, epi=3,
                  aux=_ptr(gs[0]), ldaux=H, device=dev)
         if loop:
             # dy_total(t) = dy(t) + mask[t] dfeat(t+1) W_ms and dz = relu'(z) (dy_total W2), formed here
@@ -258,12 +260,12 @@ class _SSDecodeFn(Function):
             gemm(rows, HB, FO, _ptr(dyt), 0, FO, _ptr(w2), 0, HB, _ptr(dz), HB, device=dev)
             dz.mul_(Z > 0)
         # weight gradients over all T * B rows
-        for i, (w_ih, w_hh, b_ih, b_hh, lw, lb) in enumerate(layers):
-            _wgrad(_ptr(dG[i]), 4 * H, _ptr(X[i]), H, rows, 4 * H, H, _gbuf(w_ih), dev, gb=_gbuf(b_ih),
-                   gb2=_gbuf(b_hh), keep=(dG[i], X[i]))
-            _gbuf(w_hh)  # zero state: its gradient is exactly zero, as nn.LSTM's is
+        for i, lay in enumerate(layers):
+            _wgrad(_ptr(dG[i]), 4 * H, _ptr(X[i]), H, rows, 4 * H, H, _gbuf(lay.w_ih), dev, gb=_gbuf(lay.b_ih),
+                   gb2=_gbuf(lay.b_hh), keep=(dG[i], X[i]))
+            _gbuf(lay.w_hh)  # zero state: its gradient is exactly zero, as nn.LSTM's is
             du = duL if i == nl - 1 else dX[i + 1]
-            _resln_bwd(du.view(rows, H), Hs[i].view(rows, H), X[i].view(rows, H), lw, lb,
+            _resln_bwd(du.view(rows, H), Hs[i].view(rows, H), X[i].view(rows, H), lay.ln_w, lay.ln_b,
                        stats[i][0].reshape(rows), stats[i][1].reshape(rows))
         _wgrad(_ptr(dyt), FO, _ptr(Z), HB, rows, FO, HB, _gbuf(w2), dev, gb=_gbuf(b2), keep=(dyt, Z))
         _wgrad(_ptr(dz), HB, _ptr(U), H, rows, HB, H, _gbuf(w1), dev, gb=_gbuf(b1), keep=(dz, U))
@@ -279,7 +281,7 @@ class _SSDecodeFn(Function):
 def scheduled_sampling_decode(a_s, mp, ms, mask, w_f, b_f, layers, ffn, eps=1e-5):
     """y [B, T, FO] of head_motion_generation given the sampler outputs a_s [B, T, SA].
 
-    layers: [(w_ih, w_hh, b_ih, b_hh, ln_weight, ln_bias)] of the layered LSTM (zero state each
+    layers: [forms.LstmLn] (or plain tuples in its field order) of the layered LSTM (zero state each
     frame); ffn: (w1, b1, w2, b2) of Linear -> ReLU -> Linear; mask: [T] bool (device or host)."""
     dev = a_s.device
     m = mask.to(device=dev, dtype=torch.uint8)

@@ -41,6 +41,7 @@ from . import _lib
 from . import gemm_ops
 from .gemm_ops import _dx_gemm, _wt_note, gemm
 from .launch import _ARITH, _err_flag, _gbuf, _keeps_precision, _probe, _ptr, _stream, _ws, zeros
+from .model.forms import LstmBlock
 from .wgrad_streams import beside_recurrence
 
 # time steps per chunk (the diagonal width); MRG_STACK_CHUNK overrides.  100 since the deferred weight
@@ -72,7 +73,7 @@ def _split(v, cap):
     q = (len(v) + k - 1) // k
     return [v[s:s + q] for s in range(0, len(v), q)]
 VP, CL, CI = ctypes.c_void_p, ctypes.c_long, ctypes.c_int
-_PER_LAYER = 10   # w_ih, w_hh, b_ih, b_hh, ln1 gamma, ln1 beta, w_ff, b_ff, ln2 gamma, ln2 beta
+_PER_LAYER = len(LstmBlock._fields)
 
 
 def _chunks(T, tc):
@@ -84,7 +85,8 @@ def _p(t, off=0):
 
 
 class _Chain:
-    """One modality: features [B, T, F] -> embedding -> L layers (tensors are time-major)."""
+    """One modality: features [B, T, F] -> embedding -> L layers (forms.LstmBlock each; tensors are
+    time-major)."""
 
     def __init__(self, feat, emb_w, emb_b, layers):
         self.feat, self.emb_w, self.emb_b, self.layers = feat, emb_w, emb_b, layers
@@ -259,7 +261,7 @@ def _groups(items, key, cap):
 
 class _EncoderStackFn(Function):
     """spec = (layers per chain, chunk length, eps); tensors = per chain [feat, emb_w, emb_b,
-    10 per layer]; returns the last layer's output of every chain, batch-major [B, T, H]."""
+    forms.LstmBlock's fields per layer]; returns the last layer's output of every chain, batch-major [B, T, H]."""
 
     @staticmethod
     @_keeps_precision
@@ -272,7 +274,7 @@ class _EncoderStackFn(Function):
         for L in nls:
             feat, ew, eb = tensors[k:k + 3]
             k += 3
-            layers = [tensors[k + _PER_LAYER * i:k + _PER_LAYER * (i + 1)] for i in range(L)]
+            layers = [LstmBlock._make(tensors[k + _PER_LAYER * i:k + _PER_LAYER * (i + 1)]) for i in range(L)]
             k += _PER_LAYER * L
             chains.append(_Chain(feat.contiguous(), ew, eb, layers))
         _lib.require_device(chains[0].feat)
@@ -288,17 +290,16 @@ class _EncoderStackFn(Function):
             gemm(rows, H, F, _ptr(ch.feat), 0, T * F, _ptr(ch.emb_w), 1, F, _ptr(x0), H, bias=_ptr(ch.emb_b),
                  a_hi=F, a_div=B, device=dev)
             sts = []
-            for l, (w_ih, w_hh, b_ih, b_hh, g1, be1, w_ff, b_ff, g2, be2) in enumerate(ch.layers):
-                st = dict(w_ih=w_ih, w_hh=w_hh, b_ih=b_ih, b_hh=b_hh, g1=g1, be1=be1, w_ff=w_ff, b_ff=b_ff, g2=g2,
-                          be2=be2, x=x0 if l == 0 else sts[-1]["v"],
+            for l, lay in enumerate(ch.layers):
+                st = dict(lay._asdict(), x=x0 if l == 0 else sts[-1]["v"],
                           gx=torch.empty(T, B, 4 * H, **f32), y=torch.empty(T, B, H, **f32),
                           gates=torch.empty(T, B, 4 * H, **f32), cs=torch.empty(T, B, H, **f32),
                           u=torch.empty(T, B, H, **f32), z=torch.empty(T, B, H, **f32),
                           v=torch.empty(T, B, H, **f32) if l + 1 < ch.L else None,
                           m1=torch.empty(rows, **f32), r1=torch.empty(rows, **f32),
                           m2=torch.empty(rows, **f32), r2=torch.empty(rows, **f32))
-                _wt_note(w_ih, rows)
-                _wt_note(w_ff, rows)
+                _wt_note(lay.w_ih, rows)
+                _wt_note(lay.ff_w, rows)
                 sts.append(st)
             states.append(sts)
             outs.append(torch.empty(B, T, H, **f32))
@@ -322,15 +323,15 @@ class _EncoderStackFn(Function):
                 ln1, ff, ln2 = [], [], []
                 for m, l, c, t0, t1 in grp:
                     ch, st, r0 = chains[m], states[m][l], t0 * B
-                    ln1.append((_p(st["y"], r0 * H), _p(st["x"], r0 * H), _ptr(st["g1"]), _ptr(st["be1"]),
+                    ln1.append((_p(st["y"], r0 * H), _p(st["x"], r0 * H), _ptr(st["ln1_w"]), _ptr(st["ln1_b"]),
                                 _p(st["u"], r0 * H), (H, 0, 0), _p(st["m1"], r0), _p(st["r1"], r0)))
-                    ff.append((_p(st["u"], r0 * H), st["w_ff"], _p(st["z"], r0 * H), _ptr(st["b_ff"]), None))
+                    ff.append((_p(st["u"], r0 * H), st["ff_w"], _p(st["z"], r0 * H), _ptr(st["ff_b"]), None))
                     if st["v"] is not None:
                         out, omap = _p(st["v"], r0 * H), (H, 0, 0)
                     else:   # last layer: rows (t, b) land in the batch-major output [B, T, H]
                         out, omap = _p(outs[m], t0 * H), (ch.T * H, H, B)
-                    ln2.append((_p(st["z"], r0 * H), _p(st["u"], r0 * H), _ptr(st["g2"]), _ptr(st["be2"]), out, omap,
-                                _p(st["m2"], r0), _p(st["r2"], r0)))
+                    ln2.append((_p(st["z"], r0 * H), _p(st["u"], r0 * H), _ptr(st["ln2_w"]), _ptr(st["ln2_b"]), out,
+                                omap, _p(st["m2"], r0), _p(st["r2"], r0)))
                 _bln_fwd(lib, n, H, eps, ln1)
                 _bgemm(lib, n, H, H, ff, H, H, dev=dev)
                 _bln_fwd(lib, n, H, eps, ln2)
@@ -344,8 +345,7 @@ class _EncoderStackFn(Function):
                     save.append(st[key])
         ctx.save_for_backward(*save)
         ctx.keys = ("x", "y", "gates", "cs", "u", "z", "m1", "r1", "m2", "r2")
-        ctx.params = [[{k2: st[k2] for k2 in ("w_ih", "w_hh", "b_ih", "b_hh", "g1", "be1", "w_ff", "b_ff", "g2",
-                                               "be2")} for st in sts] for sts in states]
+        ctx.params = [[{k2: st[k2] for k2 in LstmBlock._fields} for st in sts] for sts in states]
         return tuple(outs)
 
     @staticmethod
@@ -422,10 +422,10 @@ class _EncoderStackFn(Function):
                         dy, dmap = _p(douts[m], t0 * H), (ch.T * H, H, B)
                     else:
                         dy, dmap = _p(grads[m][l + 1]["dv"], r0 * H), (H, 0, 0)
-                    ln2.append((dy, dmap, _p(st["z"], r0 * H), _p(st["u"], r0 * H), _ptr(st["g2"]), _p(st["m2"], r0),
+                    ln2.append((dy, dmap, _p(st["z"], r0 * H), _p(st["u"], r0 * H), _ptr(st["ln2_w"]), _p(st["m2"], r0),
                                 _p(st["r2"], r0), _p(gr["g2"], r0 * H), _p(gr["ws2"], bo)))
-                    ff.append((_p(gr["g2"], r0 * H), st["w_ff"], _ptr(du[i]), None, _p(gr["g2"], r0 * H)))
-                    ln1.append((_ptr(du[i]), (H, 0, 0), _p(st["y"], r0 * H), _p(st["x"], r0 * H), _ptr(st["g1"]),
+                    ff.append((_p(gr["g2"], r0 * H), st["ff_w"], _ptr(du[i]), None, _p(gr["g2"], r0 * H)))
+                    ln1.append((_ptr(du[i]), (H, 0, 0), _p(st["y"], r0 * H), _p(st["x"], r0 * H), _ptr(st["ln1_w"]),
                                 _p(st["m1"], r0), _p(st["r1"], r0), _p(gr["g1"], r0 * H), _p(gr["ws1"], bo)))
                 _bln_bwd(lib, n, H, ln2)
                 _bgemm(lib, n, H, H, ff, H, H, epi=3, ldaux=H, transposed=True, dev=dev)
@@ -468,8 +468,8 @@ class _EncoderStackFn(Function):
         dG, g2, g1, dx0 = gr["dG"], gr["g2"], gr["g1"], gr["dv"]
         gbi, gbh = _gbuf(st["b_ih"]), _gbuf(st["b_hh"])
         first = gbi if gbi is not None else gbh
-        gw_ih, gw_hh, gw_ff, gb_ff = _gbuf(st["w_ih"]), _gbuf(st["w_hh"]), _gbuf(st["w_ff"]), _gbuf(st["b_ff"])
-        lns = [(gr["ws1"], _gbuf(st["g1"]), _gbuf(st["be1"])), (gr["ws2"], _gbuf(st["g2"]), _gbuf(st["be2"]))]
+        gw_ih, gw_hh, gw_ff, gb_ff = _gbuf(st["w_ih"]), _gbuf(st["w_hh"]), _gbuf(st["ff_w"]), _gbuf(st["ff_b"])
+        lns = [(gr["ws1"], _gbuf(st["ln1_w"]), _gbuf(st["ln1_b"])), (gr["ws2"], _gbuf(st["ln2_w"]), _gbuf(st["ln2_b"]))]
         emb = (_gbuf(ch.emb_w), _gbuf(ch.emb_b)) if l == 0 else (None, None)
         keep = (dG, g2, g1, dx0, st["x"], st["y"], st["u"], gr["ws1"], gr["ws2"], ch.feat)
         th = max(t0, 1)   # dW_hh pairs dG_t with y_{t-1}: t >= 1
@@ -542,8 +542,8 @@ def stack_eligible(H, B) -> bool:
 
 
 def encoder_stack(chains: Sequence[Sequence], eps: float, chunk: int = 0) -> List[torch.Tensor]:
-    """chains: [(feat [B, T, F], emb_w, emb_b, [(w_ih, w_hh, b_ih, b_hh, ln1_w, ln1_b, ff_w, ff_b, ln2_w,
-    ln2_b)] per layer)]; returns the last layer's output of every chain ([B, T, H], batch-major)."""
+    """chains: [(feat [B, T, F], emb_w, emb_b, [forms.LstmBlock, or a plain tuple in its
+    field order, per layer])]; returns the last layer's output of every chain ([B, T, H], batch-major)."""
     flat, nls = [], []
     for feat, ew, eb, layers in chains:
         flat += [feat, ew, eb]

@@ -28,11 +28,12 @@ import os
 from typing import Optional
 
 import torch
-from torch import nn
 
 from . import _lib
 from . import functional as Fn
 from .launch import _err_flag, _probe, _ptr, _stream, zeros
+from .model import forms
+from .model.metaformer import _FUSED_MIN_T
 
 F32 = torch.float32
 E_GEN, HB_GEN = 256, 64
@@ -45,21 +46,6 @@ def _arr(*ts):
     return (ctypes.c_void_p * len(ts))(*[t if isinstance(t, ctypes.c_void_p) else _ptr(t) for t in ts])
 
 
-def _ffn_parts(ff, residual: bool):
-    """(w1, b1, w2, b2[, ln]) of a FeedForward Linear -> ReLU -> Linear (with its residual LayerNorm)."""
-    seq = ff.feed_forward
-    ln = None
-    if residual:
-        from .model.layers import ResidualConnection
-        if not isinstance(seq, ResidualConnection) or seq.layer_norm is None:
-            return None
-        ln, seq = seq.layer_norm, seq.module
-    mods = list(seq.children())
-    if len(mods) != 3 or not isinstance(mods[1], nn.ReLU) or any(m.bias is None for m in (mods[0], mods[2])):
-        return None
-    return mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias, ln
-
-
 class GenPlan:
     """The parameters of Metaformer.metaformer arranged for the fused frame loop, or ``ok = False``."""
 
@@ -70,33 +56,37 @@ class GenPlan:
         if not mf._fast_eligible():
             return
         blocks = list(mf.metaformer_blocks)
-        first = mf._stack_layers(blocks[0])
+        first = forms.embedding_stack_form(blocks[0])
         if first is None or len(first[0]) != 3:
             return
         layers0, eps = first
         self.eps = eps
-        self.enc = layers0[1:]                   # block 0's audio / partner-motion stacks
+        self.enc = layers0[1:]                   # block 0's audio / partner-motion stacks ([LstmBlock] each)
         self.fe = list(mf.feature_embedding)
-        if any(e.bias is None for e in self.fe):
+        if any(e.bias is None for e in self.fe) or not self.fe[0].weight.is_cuda:
             return
         self.blocks = []
-        dummy = torch.empty(1, 1, E_GEN, device=self.fe[0].weight.device)
         for bi, blk in enumerate(blocks):
-            got = mf._stack_layers(blk) if bi else first
-            if got is None or len(got[0][0]) != 1 or got[1] != eps or any(v is None for v in got[0][0][0]):
+            got = forms.embedding_stack_form(blk) if bi else first
+            if got is None:
                 return
-            args = blk.integrator.fused_args(dummy, [dummy, dummy], [None, None], [None, None])
-            if args is None or len(args[0]) != 2 or args[5] != eps:
+            (main, *_others), blk_eps = got          # the main modality's chain: one LstmBlock per block
+            if len(main) != 1 or blk_eps != eps or any(v is None for v in main[0]):
                 return
-            ffn = _ffn_parts(blk.feedforward, True)
-            if ffn is None or ffn[0].shape[0] != HB_GEN or ffn[4].eps != eps:
+            # the frames are T = 1 calls of the fused integrator: its switches hold here too
+            integ = forms.integrator_form(blk.integrator) if (blk.integrator.use_fused and _FUSED_MIN_T == 1) else None
+            if integ is None or len(integ.integrators) != 2 or integ.eps != eps or integ.cat_w.shape[0] != E_GEN:
                 return
-            self.blocks.append({"lstm": got[0][0][0], "integ": args[0], "cat": (args[1], args[2]), "ffn": ffn})
-        out = _ffn_parts(mf.output_feedforward, False)
-        if out is None or out[0].shape[0] != HB_GEN or out[2].shape[0] > 16:
+            ffn = forms.relu_ffn_form(blk.feedforward, True)
+            if ffn is None or ffn.w1.shape[0] != HB_GEN or ffn.ln.eps != eps:
+                return
+            self.blocks.append({"lstm": main[0], "integ": integ.integrators, "cat": (integ.cat_w, integ.cat_b),
+                                "ffn": ffn})
+        out = forms.relu_ffn_form(mf.output_feedforward, False)
+        if out is None or out.w1.shape[0] != HB_GEN or out.w2.shape[0] > 16:
             return
         self.out = out
-        self.fm = out[2].shape[0]
+        self.fm = out.w2.shape[0]
         if self.fe[0].weight.shape[1] != self.fm:
             return
         self.ok = True
@@ -107,13 +97,13 @@ class GenPlan:
         N, H = x.shape[0], E_GEN
         gates = torch.empty(N, 4 * H, device=x.device, dtype=F32)
         c = torch.empty(N, H, device=x.device, dtype=F32)
-        for w_ih, _w_hh, b_ih, b_hh, l1w, l1b, fw, fb, l2w, l2b in layers:
-            g = Fn.linear(x, w_ih, b_ih)
+        for lay in layers:
+            g = Fn.linear(x, lay.w_ih, lay.b_ih)
             h = torch.empty(N, H, device=x.device, dtype=F32)
-            _lib.check(lib.mrg_lstm_cell_fwd(N, H, _ptr(g), 4 * H, _ptr(b_hh), None, _ptr(gates), _ptr(c), _ptr(h),
+            _lib.check(lib.mrg_lstm_cell_fwd(N, H, _ptr(g), 4 * H, _ptr(lay.b_hh), None, _ptr(gates), _ptr(c), _ptr(h),
                                              H, None, _stream()), "gen encoder cell")
-            y = Fn.residual_layernorm(h, x, l1w, l1b, self.eps)
-            x = Fn.residual_layernorm(Fn.linear(y, fw, fb), y, l2w, l2b, self.eps)
+            y = Fn.residual_layernorm(h, x, lay.ln1_w, lay.ln1_b, self.eps)
+            x = Fn.residual_layernorm(Fn.linear(y, lay.ff_w, lay.ff_b), y, lay.ln2_w, lay.ln2_b, self.eps)
         return x
 
     def generate(self, fb, mp, ms, mask):
@@ -128,8 +118,8 @@ class GenPlan:
         # per block and integrator: out_proj(V(kv)), the attention output at one visible key
         att = []
         for blk in self.blocks:
-            att.append([Fn.linear(Fn.linear(kv, iw[2 * E:], ib[2 * E:]), ow, ob)
-                        for kv, (iw, ib, ow, ob, *_r) in zip(others, blk["integ"])])
+            att.append([Fn.linear(Fn.linear(kv, ip.in_w[2 * E:], ip.in_b[2 * E:]), ip.out_w, ip.out_b)
+                        for kv, ip in zip(others, blk["integ"])])
         msc = ms.reshape(T, B, self.fm).contiguous()
         # the kernel reads one byte per frame (a device bool tensor as it is: refreshed per graph replay)
         mask_u8 = mask if (mask.device == dev and mask.dtype in (torch.bool, torch.uint8)) \
@@ -145,21 +135,18 @@ class GenPlan:
         # argument tuples made once (the frame loop only varies the frame pointers)
         calls = []
         for bi, blk in enumerate(self.blocks):
-            w_ih, _w_hh, b_ih, b_hh, l1w, l1b, fw, fbias, l2w, l2b = blk["lstm"]
-            i0, i1 = blk["integ"]
-            cw, cb = blk["cat"]
-            w1, b1, w2, b2, fln = blk["ffn"]
-            prev = self.blocks[bi - 1]["ffn"][4] if bi else None
+            lstm, (i0, i1), (cw, cb), ffn = blk["lstm"], blk["integ"], blk["cat"], blk["ffn"]
+            prev = self.blocks[bi - 1]["ffn"].ln if bi else None
             calls.append(dict(
-                lstm=(w_ih, b_ih, b_hh, prev),
-                lin0=(_arr(hh), _arr(xb), _arr(l1w), _arr(l1b), _arr(fw), _arr(fbias)),
-                lin1=(_arr(z), _arr(y), _arr(l2w), _arr(l2b), _arr(i0[4], i1[4]), _arr(i0[5], i1[5]),
-                      _arr(i0[6], i1[6]), _arr(i0[7], i1[7])),
-                lin2=(_arr(_ptr(z01), _ptr(z01, E)), _arr(_ptr(y01), _ptr(y01, E)), _arr(i0[8], i1[8]),
-                      _arr(i0[9], i1[9]), _arr(cw), _arr(cb)),
-                ffn=(w1, b1, w2, b2)))
-        ow1, ob1, ow2, ob2, _ = self.out
-        lastln = self.blocks[-1]["ffn"][4]
+                lstm=(lstm.w_ih, lstm.b_ih, lstm.b_hh, prev),
+                lin0=(_arr(hh), _arr(xb), _arr(lstm.ln1_w), _arr(lstm.ln1_b), _arr(lstm.ff_w), _arr(lstm.ff_b)),
+                lin1=(_arr(z), _arr(y), _arr(lstm.ln2_w), _arr(lstm.ln2_b), _arr(i0.ln1_w, i1.ln1_w),
+                      _arr(i0.ln1_b, i1.ln1_b), _arr(i0.ff_w, i1.ff_w), _arr(i0.ff_b, i1.ff_b)),
+                lin2=(_arr(_ptr(z01), _ptr(z01, E)), _arr(_ptr(y01), _ptr(y01, E)), _arr(i0.ln2_w, i1.ln2_w),
+                      _arr(i0.ln2_b, i1.ln2_b), _arr(cw), _arr(cb)),
+                ffn=ffn[:4]))
+        out = self.out
+        lastln = self.blocks[-1]["ffn"].ln
         # algorithmic FLOPs of each launch (2 x rows x outputs x K; the LayerNorms are O(rows x E))
         f_lstm, f_lin0 = 2.0 * B * 4 * E * E, 2.0 * B * E * E
         f_lin1, f_lin2 = 2.0 * B * 2 * E * E, 2.0 * B * E * 2 * E
@@ -197,8 +184,8 @@ class GenPlan:
                                                _ptr(b2), _ptr(zf), None, 0, None, None, None, t, st), "gen ffn")
             with _probe("gen", f_out):
                 _lib.check(lib.mrg_gen_ffn(B, self.fm, _ptr(zf), _ptr(m3), _ptr(lastln.weight), _ptr(lastln.bias),
-                                           eps, _ptr(ow1), _ptr(ob1), _ptr(ow2), _ptr(ob2), None, _ptr(pred),
-                                           T * self.fm, _ptr(ms_in), _ptr(msc[t]), _ptr(mask_u8), t, st),
+                                           eps, _ptr(out.w1), _ptr(out.b1), _ptr(out.w2), _ptr(out.b2), None,
+                                           _ptr(pred), T * self.fm, _ptr(ms_in), _ptr(msc[t]), _ptr(mask_u8), t, st),
                            "gen output")
         return pred
 
@@ -206,17 +193,14 @@ class GenPlan:
         """The frame loop in one persistent launch (mrg_gen_loop; pointer table order in include/mrg.h)."""
         ptrs = []
         for bi, blk in enumerate(self.blocks):
-            w_ih, _w_hh, b_ih, b_hh, l1w, l1b, fw, fbias, l2w, l2b = blk["lstm"]
-            i0, i1 = blk["integ"]
-            cw, cb = blk["cat"]
-            w1, b1, w2, b2, fln = blk["ffn"]
-            ptrs += [w_ih, b_ih, b_hh, l1w, l1b, fw, fbias, l2w, l2b]
-            for ip in (i0, i1):
-                ptrs += [ip[4], ip[5], ip[6], ip[7], ip[8], ip[9]]
-            ptrs += [cw, cb, w1, b1, w2, b2, fln.weight, fln.bias, att[bi][0], att[bi][1]]
-        ow1, ob1, ow2, ob2, _ = self.out
-        fe0 = self.fe[0]
-        ptrs += [fe0.weight, fe0.bias, ow1, ob1, ow2, ob2]
+            lstm, ffn = blk["lstm"], blk["ffn"]
+            ptrs += [lstm.w_ih, lstm.b_ih, lstm.b_hh, lstm.ln1_w, lstm.ln1_b, lstm.ff_w, lstm.ff_b, lstm.ln2_w,
+                     lstm.ln2_b]
+            for ip in blk["integ"]:
+                ptrs += [ip.ln1_w, ip.ln1_b, ip.ff_w, ip.ff_b, ip.ln2_w, ip.ln2_b]
+            ptrs += [*blk["cat"], ffn.w1, ffn.b1, ffn.w2, ffn.b2, ffn.ln.weight, ffn.ln.bias, att[bi][0], att[bi][1]]
+        fe0, out = self.fe[0], self.out
+        ptrs += [fe0.weight, fe0.bias, out.w1, out.b1, out.w2, out.b2]
         ring = zeros(max(1, lib.mrg_gen_loop_ring_bytes(B) // 8), dtype=torch.int64, device=msc.device)
         E = E_GEN
         flop = T * (len(self.blocks) * 2.0 * B * (4 * E * E + E * E + 2 * E * E + 2 * E * E + 2 * HB_GEN * E)

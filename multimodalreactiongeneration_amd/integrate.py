@@ -34,9 +34,10 @@ from . import gemm_ops
 from .attention import visible_pairs
 from .gemm_ops import _dx_gemm, _wt_note, gemm
 from .launch import _ARITH, _gbuf, _keeps_precision, _probe, _ptr, _stream, _ws
+from .model.forms import Integrator
 
 VP, CL, CI = ctypes.c_void_p, ctypes.c_long, ctypes.c_int
-_PER = 10   # in_w, in_b, out_w, out_b, ln1 w, ln1 b, ff w, ff b, ln2 w, ln2 b
+_PER = len(Integrator._fields)
 
 
 def _arr(ct, v):
@@ -114,7 +115,8 @@ class KVSink:
 
 class _IntegrateFn(Function):
     """spec = (n, heads, causal, eps); tensors = q, kv_0..kv_{n-1}, qpad_0..qpad_{n-1},
-    kpad_0..kpad_{n-1}, 10 per integrator, cat_w, cat_b (pads: uint8 [B, T] flags or None)."""
+    kpad_0..kpad_{n-1}, forms.Integrator's fields per integrator, cat_w, cat_b (pads: uint8 [B, T] flags
+    or None)."""
 
     @staticmethod
     @_keeps_precision
@@ -124,7 +126,7 @@ class _IntegrateFn(Function):
         kvs = list(t[1:1 + n])
         qpads = list(t[1 + n:1 + 2 * n])
         kpads = list(t[1 + 2 * n:1 + 3 * n])
-        P = [t[1 + 3 * n + _PER * i:1 + 3 * n + _PER * (i + 1)] for i in range(n)]
+        P = [Integrator._make(t[1 + 3 * n + _PER * i:1 + 3 * n + _PER * (i + 1)]) for i in range(n)]
         cat_w, cat_b = t[1 + 3 * n + _PER * n:]
         _lib.require_device(q_in)
         dev = q_in.device
@@ -135,8 +137,9 @@ class _IntegrateFn(Function):
         f32 = dict(device=dev, dtype=torch.float32)
         q2 = q_in.contiguous()
         kv2 = [kv.contiguous() for kv in kvs]
+        q_w, kv_w = [p.q_w for p in P], [p.kv_w for p in P]
         Q = torch.empty(n, N, E, **f32)
-        _bgemm(N, E, E, [(_ptr(q2), P[i][0][:E], _ptr(Q[i]), _ptr(P[i][1]), None) for i in range(n)], E, E, dev=dev)
+        _bgemm(N, E, E, [(_ptr(q2), q_w[i], _ptr(Q[i]), _ptr(P[i].q_b), None) for i in range(n)], E, E, dev=dev)
         KV = []
         for i in range(n):
             Tk = kv2[i].shape[1]
@@ -145,7 +148,7 @@ class _IntegrateFn(Function):
         groups = [list(range(n))] if same_k else [[i] for i in range(n)]
         for g in groups:
             Nk = B * kv2[g[0]].shape[1]
-            _bgemm(Nk, 2 * E, E, [(_ptr(kv2[i]), P[i][0][E:], _ptr(KV[i]), _p(P[i][1], E), None) for i in g],
+            _bgemm(Nk, 2 * E, E, [(_ptr(kv2[i]), kv_w[i], _ptr(KV[i]), _ptr(P[i].kv_b), None) for i in g],
                    E, 2 * E, dev=dev)
         O = torch.empty(n, N, E, **f32)
         lse = torch.empty(n, B, heads, Tq, **f32)
@@ -158,22 +161,22 @@ class _IntegrateFn(Function):
                                            _ptr(lse[i]), _ptr(qpads[i]), _ptr(kpads[i]), int(causal), scale, _stream())
             _lib.check(rc, "attention fwd (integrator)")
         A = torch.empty(n, N, E, **f32)    # attention outputs after out_proj
-        _bgemm(N, E, E, [(_ptr(O[i]), P[i][2], _ptr(A[i]), _ptr(P[i][3]), None) for i in range(n)], E, E, dev=dev)
+        _bgemm(N, E, E, [(_ptr(O[i]), P[i].out_w, _ptr(A[i]), _ptr(P[i].out_b), None) for i in range(n)], E, E, dev=dev)
         U = torch.empty(n, N, E, **f32)
         m1, r1 = torch.empty(n, N, **f32), torch.empty(n, N, **f32)
-        _bln_fwd(N, E, eps, [(_ptr(A[i]), _ptr(q2), _ptr(P[i][4]), _ptr(P[i][5]), _ptr(U[i]), (E, 0, 0),
+        _bln_fwd(N, E, eps, [(_ptr(A[i]), _ptr(q2), _ptr(P[i].ln1_w), _ptr(P[i].ln1_b), _ptr(U[i]), (E, 0, 0),
                               _ptr(m1[i]), _ptr(r1[i])) for i in range(n)])
         Z = torch.empty(n, N, E, **f32)
-        _bgemm(N, E, E, [(_ptr(U[i]), P[i][6], _ptr(Z[i]), _ptr(P[i][7]), None) for i in range(n)], E, E, dev=dev)
+        _bgemm(N, E, E, [(_ptr(U[i]), P[i].ff_w, _ptr(Z[i]), _ptr(P[i].ff_b), None) for i in range(n)], E, E, dev=dev)
         cat = torch.empty(N, n * E, **f32)
         m2, r2 = torch.empty(n, N, **f32), torch.empty(n, N, **f32)
-        _bln_fwd(N, E, eps, [(_ptr(Z[i]), _ptr(U[i]), _ptr(P[i][8]), _ptr(P[i][9]), _p(cat, i * E), (n * E, 0, 0),
+        _bln_fwd(N, E, eps, [(_ptr(Z[i]), _ptr(U[i]), _ptr(P[i].ln2_w), _ptr(P[i].ln2_b), _p(cat, i * E), (n * E, 0, 0),
                               _ptr(m2[i]), _ptr(r2[i])) for i in range(n)])
         out = torch.empty(B, Tq, E, **f32)
         gemm(N, E, n * E, _ptr(cat), 0, n * E, _ptr(cat_w), 1, n * E, _ptr(out), E, bias=_ptr(cat_b), device=dev)
         _wt_note(cat_w, N)
         for i in range(n):
-            for w, rows in ((P[i][0][:E], N), (P[i][2], N), (P[i][6], N), (P[i][0][E:], B * kv2[i].shape[1])):
+            for w, rows in ((q_w[i], N), (P[i].out_w, N), (P[i].ff_w, N), (kv_w[i], B * kv2[i].shape[1])):
                 _wt_note(w, rows)
         ctx.save_for_backward(q2, Q, O, lse, A, U, m1, r1, Z, m2, r2, cat, *qpads, *kv2, *KV, *kpads)
         ctx.params = (P, cat_w, cat_b)
@@ -204,16 +207,16 @@ class _IntegrateFn(Function):
         wsb = lib.mrg_residual_layernorm_bwd_workspace_bytes(N, E) // 4
         ws2, ws1 = torch.empty(n, wsb, **f32), torch.empty(n, wsb, **f32)
         G2 = torch.empty(n, N, E, **f32)
-        _bln_bwd(N, E, [(_p(dcat, i * E), (n * E, 0, 0), _ptr(Z[i]), _ptr(U[i]), _ptr(P[i][8]), _ptr(m2[i]),
+        _bln_bwd(N, E, [(_p(dcat, i * E), (n * E, 0, 0), _ptr(Z[i]), _ptr(U[i]), _ptr(P[i].ln2_w), _ptr(m2[i]),
                          _ptr(r2[i]), _ptr(G2[i]), _ptr(ws2[i])) for i in range(n)])
         dU = torch.empty(n, N, E, **f32)      # g2 W_ff + g2 (residual branch in the epilogue)
-        _bgemm(N, E, E, [(_ptr(G2[i]), P[i][6], _ptr(dU[i]), None, _ptr(G2[i])) for i in range(n)], E, E,
+        _bgemm(N, E, E, [(_ptr(G2[i]), P[i].ff_w, _ptr(dU[i]), None, _ptr(G2[i])) for i in range(n)], E, E,
                epi=3, ldaux=E, transposed=True, dev=dev)
         G1 = torch.empty(n, N, E, **f32)
-        _bln_bwd(N, E, [(_ptr(dU[i]), (E, 0, 0), _ptr(A[i]), _ptr(q2), _ptr(P[i][4]), _ptr(m1[i]), _ptr(r1[i]),
+        _bln_bwd(N, E, [(_ptr(dU[i]), (E, 0, 0), _ptr(A[i]), _ptr(q2), _ptr(P[i].ln1_w), _ptr(m1[i]), _ptr(r1[i]),
                          _ptr(G1[i]), _ptr(ws1[i])) for i in range(n)])
         dO = torch.empty(n, N, E, **f32)
-        _bgemm(N, E, E, [(_ptr(G1[i]), P[i][2], _ptr(dO[i]), None, None) for i in range(n)], E, E,
+        _bgemm(N, E, E, [(_ptr(G1[i]), P[i].out_w, _ptr(dO[i]), None, None) for i in range(n)], E, E,
                transposed=True, dev=dev)
         dQ = torch.empty(n, N, E, **f32)
         dKV = [torch.empty(B, kv.shape[1], 2 * E, **f32) for kv in kv2]
@@ -231,7 +234,7 @@ class _IntegrateFn(Function):
         if ctx.q_need:   # dq = sum_i (dQ_i W_q_i + g1_i): two epilogue-3 GEMMs into one buffer
             dq = torch.empty(B, Tq, E, **f32)
             for i in range(n):
-                _dx_gemm(N, E, E, _ptr(dQ[i]), E, P[i][0][:E], _ptr(dq), E, epi=3, aux=_ptr(G1[i]), ldaux=E,
+                _dx_gemm(N, E, E, _ptr(dQ[i]), E, P[i].q_w, _ptr(dq), E, epi=3, aux=_ptr(G1[i]), ldaux=E,
                          beta=0.0 if i == 0 else 1.0, device=dev)
         dkv = []
         for i in range(n):
@@ -242,13 +245,13 @@ class _IntegrateFn(Function):
             sink = ctx.sinks[i]
             if sink is None:   # no draining producer: this consumer's own part, summed by autograd
                 g = torch.empty(B, Tk, E, **f32)
-                _dx_gemm(B * Tk, E, 2 * E, _ptr(dKV[i]), 2 * E, P[i][0][E:], _ptr(g), E, device=dev)
+                _dx_gemm(B * Tk, E, 2 * E, _ptr(dKV[i]), 2 * E, P[i].kv_w, _ptr(g), E, device=dev)
                 dkv.append(g)
                 continue
             first = sink.begin_write()
             if first:
                 sink.buf = torch.empty(B, Tk, E, **f32)
-            _dx_gemm(B * Tk, E, 2 * E, _ptr(dKV[i]), 2 * E, P[i][0][E:], _ptr(sink.buf), E,
+            _dx_gemm(B * Tk, E, 2 * E, _ptr(dKV[i]), 2 * E, P[i].kv_w, _ptr(sink.buf), E,
                      beta=0.0 if first else 1.0, device=dev)
             sink.written += 1
             dkv.append(None)   # the producer drains the sum (KVSink)
@@ -262,10 +265,7 @@ class _IntegrateFn(Function):
         gcw, gcb = _gbuf(cat_w), _gbuf(cat_b)
         per = []
         for i in range(n):
-            gw, gb = _gbuf(P[i][0]), _gbuf(P[i][1])
-            per.append(dict(in_w=gw, in_b=gb, out_w=_gbuf(P[i][2]), out_b=_gbuf(P[i][3]), g1=_gbuf(P[i][4]),
-                            b1=_gbuf(P[i][5]), ff_w=_gbuf(P[i][6]), ff_b=_gbuf(P[i][7]), g2=_gbuf(P[i][8]),
-                            b2=_gbuf(P[i][9])))
+            per.append({k: _gbuf(w) for k, w in zip(Integrator._fields, P[i])})
         keep = (do2, cat, G2, U, G1, O, dQ, q2, ws1, ws2, *dKV, *kv2)
 
         def wg(dY, ldy, X, ldx, rows, Nout, Nin, gw, gb=None):
@@ -288,8 +288,8 @@ class _IntegrateFn(Function):
             wg(_ptr(do2), E, _ptr(cat), n * E, N, E, n * E, gcw, gcb)
             for i, g in enumerate(per):
                 wg(_ptr(G2[i]), E, _ptr(U[i]), E, N, E, E, g["ff_w"], g["ff_b"])
-                reduce(ws2[i], g["g2"], g["b2"])
-                reduce(ws1[i], g["g1"], g["b1"])
+                reduce(ws2[i], g["ln2_w"], g["ln2_b"])
+                reduce(ws1[i], g["ln1_w"], g["ln1_b"])
                 wg(_ptr(G1[i]), E, _ptr(O[i]), E, N, E, E, g["out_w"], g["out_b"])
                 wg(_ptr(dQ[i]), E, _ptr(q2), E, N, E, E, None if g["in_w"] is None else g["in_w"][:E],
                    None if g["in_b"] is None else g["in_b"][:E])
@@ -320,8 +320,7 @@ def _bln_bwd(rows, E, items):
 def integrate(q: torch.Tensor, kvs: Sequence[torch.Tensor], qpads, kpads, params: Sequence[Sequence[torch.Tensor]],
               cat_w, cat_b, heads: int, causal: bool, eps: float) -> torch.Tensor:
     """cat_linear(cat_i LN2_i(FF_i(LN1_i(MHA_i(q, kv_i) + q)) + ...)): see the module docstring.
-    params[i] = (in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias, ln1.weight, ln1.bias,
-    ff.weight, ff.bias, ln2.weight, ln2.bias)."""
+    params[i]: a forms.Integrator, or a plain tuple in its field order."""
     n = len(kvs)
     flat = [q, *kvs, *qpads, *kpads]
     for p in params:

@@ -18,10 +18,10 @@ import torch
 from torch import nn
 
 from .. import functional as Fn
+from . import forms
 from .layers import Linear, FeedForward, ResidualConnection
-from .masks import gen_attention_mask  # noqa: F401  (re-export, reference location)
-from .mixers import (MixerLayerdFactory, LSTMMixerLayerd, MHAMixerLayerd, LSTMMixerBlock,
-                     split_state)
+from .masks import BlockCausalMask, gen_attention_mask  # noqa: F401  (re-export, reference location)
+from .mixers import MixerLayerdFactory, LSTMMixerBlock, split_state
 
 
 def check_form_modal_num(modal_num: int, sameone, msg: str = None) -> list:
@@ -94,67 +94,44 @@ class IntegrateModalBlock(nn.Module):
     use_fused = os.environ.get("MRG_FUSED_INTEGRATOR", "1") == "1"
 
     def _fused(self, main_modal, other_modals, attn_mask, hxs):
-        """integrate.integrate(...) when the block is inside its form (single-block MHA layerds with
-        residual LN, one-Linear residual-LN FeedForward, block-causal or no mask, no state), else None."""
+        """integrate.integrate(...) when the block is inside its form (forms.integrator_form) and the
+        call is one the fused op takes (fused_args), else None."""
         from ..integrate import integrate
         args = self.fused_args(main_modal, other_modals, attn_mask, hxs)
         if args is None:
             return None
-        params, cw, cb, heads, causal, eps, qpads, kpads = args
-        return integrate(main_modal, list(other_modals), qpads, kpads, params, cw, cb, heads, causal, eps)
+        return integrate(main_modal, list(other_modals), args.qpads, args.kpads, args.params, args.cat_w,
+                         args.cat_b, args.heads, args.causal, args.eps)
 
     def fused_args(self, main_modal, other_modals, attn_mask, hxs):
-        """(per-integrator parameter tuples, cat_w, cat_b, heads, causal, eps, qpads, kpads) of the fused
-        form (integrate.py), or None when the block is outside it."""
-        from .masks import BlockCausalMask
+        """forms.FusedIntegratorArgs of the fused form (integrate.py), or None when the block is outside
+        it (forms.integrator_form) or this call is: the switch off, a carried state, inputs that are not
+        [B, T >= _FUSED_MIN_T, E] / [B, Tk, E] device tensors, an attention dropout that would drop, a
+        mask that is not block-causal, or masks on some integrators only."""
         if not (self.use_fused and isinstance(main_modal, torch.Tensor) and main_modal.is_cuda
                 and main_modal.dim() == 3 and main_modal.shape[1] >= _FUSED_MIN_T and all(h is None for h in hxs)):
             return None
+        form = forms.integrator_form(self)
         B, T, E = main_modal.shape
-        n = len(self.integrators)
-        cw = self.cat_linear.weight
-        if self.cat_linear.bias is None or tuple(cw.shape) != (E, n * E):
+        if form is None or form.cat_w.shape[0] != E:
             return None
-        params, heads, eps, masks = [], set(), set(), []
-        for integ, kv, m in zip(self.integrators, other_modals, attn_mask):
-            if (integ.input_projection is not None or integ.output_projection is not None or integ.self_attention
-                    or len(integ.mixer) != 1):
-                return None
-            blk = integ.mixer[0]
-            res, ffw = blk.mixer, getattr(blk.feed_forward, "feed_forward", None)
-            if not (isinstance(res, ResidualConnection) and res.layer_norm is not None and len(res.module.mixer) == 1):
-                return None
-            if res.module.mixer[0].nonlinearity is not None:   # Q7: the module path mirrors it
-                return None
-            mha = res.module.mixer[0].mha
-            if (not mha.batch_first or (mha.dropout and mha.training) or mha.in_proj_bias is None
-                    or tuple(mha.in_proj_weight.shape) != (3 * E, E) or mha.out_proj.bias is None
-                    or getattr(mha, "bias_k", None) is not None):
-                return None
-            if not (isinstance(ffw, ResidualConnection) and ffw.layer_norm is not None):
-                return None
-            mods = list(ffw.module.children())
-            if len(mods) != 1 or not isinstance(mods[0], nn.Linear) or mods[0].bias is None:
+        masks = []
+        for mha, kv, m in zip(form.attentions, other_modals, attn_mask):
+            if mha.dropout and mha.training:
                 return None
             if not (isinstance(kv, torch.Tensor) and kv.dim() == 3 and kv.shape[0] == B and kv.shape[2] == E
                     and kv.is_cuda):
                 return None
             if m is not None and not isinstance(m, BlockCausalMask):
                 return None
-            heads.add(mha.num_heads)
-            eps.update((res.layer_norm.eps, ffw.layer_norm.eps))
             masks.append(m)
-            params.append((mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias,
-                           res.layer_norm.weight, res.layer_norm.bias, mods[0].weight, mods[0].bias,
-                           ffw.layer_norm.weight, ffw.layer_norm.bias))
-        if len(heads) != 1 or len(eps) != 1 or E % next(iter(heads)) != 0:
-            return None
         causal = masks[0] is not None
-        if any((m is not None) != causal for m in masks):
+        if len(masks) != len(form.integrators) or any((m is not None) != causal for m in masks):
             return None
         qpads = [m.main_pad if causal else None for m in masks]
         kpads = [m.other_pad if causal else None for m in masks]
-        return params, cw, self.cat_linear.bias, heads.pop(), causal, eps.pop(), qpads, kpads
+        return forms.FusedIntegratorArgs(form.integrators, form.cat_w, form.cat_b, form.heads, causal, form.eps,
+                                         qpads, kpads)
 
     def forward(self, main_modal, other_modals, attn_mask=None, hxs=None):
         other_modals, attn_mask, hxs = self.check_form_input(other_modals, attn_mask, hxs)
@@ -277,35 +254,28 @@ class MultiModalMetaformer(nn.Module):
             for b in blocks:   # every fused schedule declines such a model, the integrator's too
                 b.integrator.use_fused = False
 
-    # ---- MI355X schedule for the first block's embedding (batched recurrences)
+    # ---- MI355X schedule for a block's embedding (batched recurrences)
     def _fast_first_embedding(self, block: MultiModalMetaformerBlock, mods: List[torch.Tensor]):
-        layerds = list(block.embedding.modal_embeddings)
-        if not all(isinstance(l, LSTMMixerLayerd) and l.input_projection is None and l.output_projection is None
-                   for l in layerds):
-            return None
-        chains = [list(l.mixer) for l in layerds]
-        if not all(isinstance(m, LSTMMixerBlock) and isinstance(m.mixer, ResidualConnection) for c in chains for m in c):
-            return None
+        """Only reached after _fast_eligible, which established forms.residual_lstm for every mixer
+        block below: no structural check is repeated here."""
+        chains = [[(m.feed_forward, *forms.residual_lstm_form(m)) for m in l.mixer]
+                  for l in block.embedding.modal_embeddings]
         xs = list(mods)
         depth = max(len(c) for c in chains)
         for layer in range(depth):
             active = [i for i, c in enumerate(chains) if layer < len(c)]
             groups = {}
             for i in active:
-                groups.setdefault((tuple(xs[i].shape), chains[i][layer].lstm_params()[1].shape[1]), []).append(i)
+                groups.setdefault((tuple(xs[i].shape), chains[i][layer][1].w_hh.shape[1]), []).append(i)
             for idxs in groups.values():
                 # at most two recurrences per launch: two batch-tile-2 problems fill the chip's
                 # 512 resident workgroups; three would need batch tiles of 4 (longer GEMV per step)
                 for start in range(0, len(idxs), 2):
                     part = idxs[start:start + 2]
                     # LN(LSTM(x) + x) fused per problem, then each block's FeedForward (fused too)
-                    probs = []
-                    for i in part:
-                        ln = chains[i][layer].mixer.layer_norm
-                        probs.append((xs[i], *chains[i][layer].lstm_params(), ln.weight, ln.bias, ln.eps))
-                    us = Fn.lstm_layers_batched(probs)
+                    us = Fn.lstm_layers_batched([(xs[i], *chains[i][layer][1], chains[i][layer][2]) for i in part])
                     for i, u in zip(part, us):
-                        xs[i] = chains[i][layer].feed_forward(u)
+                        xs[i] = chains[i][layer][0](u)
         return xs
 
     # ---- MI355X schedule: block 0's embedding stacks as one layer-wavefront (encoder_stack.py: one
@@ -314,31 +284,9 @@ class MultiModalMetaformer(nn.Module):
     use_encoder_stack = os.environ.get("MRG_ENCODER_STACK", "1") == "1"
 
     def _stack_layers(self, block: MultiModalMetaformerBlock):
-        """Per modality the (w_ih, w_hh, b_ih, b_hh, ln1, ff, ln2) tensors of block 0's LSTM blocks, or
-        None when a block is outside the stack's form (LSTM 1-layer unidirectional H -> H, residual LN,
-        FeedForward = one Linear + residual LN, one LayerNorm eps)."""
-        from torch import nn as _nn
-        out, eps = [], set()
-        for lay in block.embedding.modal_embeddings:
-            layers = []
-            for mb in lay.mixer:
-                lstm = mb.mixer.module.mixer if isinstance(mb.mixer, ResidualConnection) else None
-                ff = getattr(mb.feed_forward, "feed_forward", None)
-                if lstm is None or lstm.num_layers != 1 or lstm.bidirectional or mb.mixer.layer_norm is None:
-                    return None
-                if lstm.input_size != lstm.hidden_size or not isinstance(ff, ResidualConnection) or ff.layer_norm is None:
-                    return None
-                mods = list(ff.module.children())
-                if len(mods) != 1 or not isinstance(mods[0], _nn.Linear) or mods[0].bias is None:
-                    return None
-                ln1, ln2 = mb.mixer.layer_norm, ff.layer_norm
-                eps.update((ln1.eps, ln2.eps))
-                layers.append((*lstm.direction_params(0), ln1.weight, ln1.bias, mods[0].weight, mods[0].bias,
-                               ln2.weight, ln2.bias))
-            out.append(layers)
-        if len(eps) != 1:
-            return None
-        return out, eps.pop()
+        """forms.embedding_stack_form: per modality the forms.LstmBlocks of the block's LSTM stacks and
+        their LayerNorm eps, or None outside the encoder stack's form."""
+        return forms.embedding_stack_form(block)
 
     def _stack_first_block(self, block, feats):
         """Block 0's embeddings (feature Linear + every LSTM block of every modality) as one wavefront, or
@@ -376,23 +324,16 @@ class MultiModalMetaformer(nn.Module):
         return got
 
     def _fast_eligible(self) -> bool:
+        """Every embedding of every block is an LSTM layerd without projections whose blocks are
+        LN(LSTM(x) + x) over one unidirectional layer (forms.residual_lstm), and nothing in the
+        model is module-path-only."""
         if self.interlayer_residual or self._module_path_only():
             return False
         for block in self.metaformer_blocks:
             for lay in block.embedding.modal_embeddings:
-                if not (isinstance(lay, LSTMMixerLayerd) and lay.input_projection is None
-                        and lay.output_projection is None):
+                chain = forms.lstm_chain(lay)
+                if chain is None or any(forms.residual_lstm(m) is None for m in chain):
                     return False
-                for m in lay.mixer:
-                    if not (isinstance(m, LSTMMixerBlock) and isinstance(m.mixer, ResidualConnection)
-                            and m.mixer.layer_norm is not None):
-                        return False
-                    # the fused LN(LSTM(x) + x) takes layer 0's parameters only: a stacked or
-                    # bidirectional LSTM (num_internal_layer > 1, with its inter-layer dropout) runs
-                    # through layers.LSTM on the module path
-                    lstm = m.mixer.module.mixer
-                    if lstm.num_layers != 1 or lstm.bidirectional:
-                        return False
         return True
 
     def forward(self, main_modal, other_modals, hx=None, main_modal_others=None, other_modals_others=None,

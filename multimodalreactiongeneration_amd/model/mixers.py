@@ -68,8 +68,9 @@ class LSTMMixer(Mixer):
 
     def fused_residual_ln(self, ln, x, hn=None):
         """LN(LSTM(x) + x) in one op when the LSTM is one unidirectional layer from a zero state."""
+        from .forms import one_layer_unidirectional
         m = self.mixer
-        if hn is not None or m.num_layers != 1 or m.bidirectional or not isinstance(x, torch.Tensor):
+        if hn is not None or not one_layer_unidirectional(m) or not isinstance(x, torch.Tensor):
             return None
         u, hT, cT = Fn.lstm_residual_layernorm(x, *m.direction_params(0), ln.weight, ln.bias, ln.eps)
         return u, (hT.unsqueeze(0), cT.unsqueeze(0))
@@ -192,10 +193,6 @@ class LSTMMixerBlock(MixerBlock):
             self.mixer = ResidualConnection(self.mixer, residual_layer_norm, hidden_size)
         self.feed_forward = FeedForward(hidden_size, bottleneck_size, None, nonlinearity, residual,
                                         residual_layer_norm, bias, device, dtype)
-
-    def lstm_params(self):
-        m = self.mixer.module if isinstance(self.mixer, ResidualConnection) else self.mixer
-        return m.mixer.direction_params(0)
 
     def forward(self, x, hx=None, prev_hx=None):
         if isinstance(x, (tuple, list)):

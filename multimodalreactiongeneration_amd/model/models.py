@@ -37,8 +37,8 @@ from ..launch import _ARITH
 from ..configs import as_attr
 from ..metrics import MultiTargetMetrics
 from ..optim import FusedAdamW, FusedSGD
-from .layers import (Linear, LSTMSampler, LSTMLayerd, MultimodalAttention, ResidualConnection, paired_lstm_layerd,
-                     run_sequential_ffn)
+from . import forms
+from .layers import Linear, LSTMSampler, LSTMLayerd, MultimodalAttention, paired_lstm_layerd, run_sequential_ffn
 from .masks import gen_attention_mask
 from .metaformer import MultiModalMetaformer
 from .mixers import mixer_layerd_argments_select, feedforward_block_argments
@@ -532,34 +532,9 @@ class LSTMwithSample(LightningSurface):
     use_fused_decode = True
 
     def _fused_params(self):
-        """Parameters of the fused decode, or None when this configuration is outside it (the
-        per-frame path above then runs): layered blocks = residual LN around a 1-layer
-        unidirectional LSTM without mixing or feed-forward, FFN = Linear -> ReLU -> Linear."""
-        try:
-            layers = []
-            for blk in self.layerd_lstm.lstm_layered:
-                rc = blk.lstm_module
-                if blk.use_feed_forward or not isinstance(rc, ResidualConnection) or rc.layer_norm is None:
-                    return None
-                mod = rc.module
-                if mod.mixer is not None:
-                    return None
-                lstm = mod.lstm_module
-                if lstm.num_layers != 1 or lstm.bidirectional:
-                    return None
-                ln = rc.layer_norm
-                layers.append((*lstm.direction_params(0), ln.weight, ln.bias))
-            ff = list(self.feed_forward.children())
-            if len(ff) != 3 or not isinstance(ff[1], nn.ReLU):
-                return None
-            H = self.feature_projection.weight.shape[0]
-            if not (4 <= H <= 256 and H % 4 == 0 and ff[0].weight.shape[0] <= 64 and ff[2].weight.shape[0] <= 8):
-                return None
-            if any(p[4].shape[0] != H or abs(rc.layer_norm.eps - 1e-5) > 0 for p in layers):
-                return None
-            return layers, (ff[0].weight, ff[0].bias, ff[2].weight, ff[2].bias)
-        except AttributeError:
-            return None
+        """forms.decode_form: ([LstmLn], (w1, b1, w2, b2), eps) of the fused decode, or None when this
+        configuration is outside it (the per-frame path above then runs)."""
+        return forms.decode_form(self)
 
     def _fused_prediction(self, batch, sampling_mask):
         """head_motion_generation with the sampler over the whole audio sequence in one pass and the
@@ -573,10 +548,10 @@ class LSTMwithSample(LightningSurface):
         lead, T = batch[4][0].shape[1], batch[1][0].shape[1]
         if a.shape[1] != lead + T:
             raise RuntimeError(f"acoustic: {a.shape} motion frames: {lead} + {T} ratio: {self.ratio}")
-        layers, ffn = self._fused_params()
+        layers, ffn, eps = self._fused_params()
         return scheduled_sampling_decode(a[:, lead:], batch[1][0], batch[2][0], sampling_mask,
                                          self.feature_projection.weight, self.feature_projection.bias,
-                                         layers, ffn, eps=self.layerd_lstm.lstm_layered[0].lstm_module.layer_norm.eps)
+                                         layers, ffn, eps=eps)
 
 
 class AcousticEncoder(nn.Module):
