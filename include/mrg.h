@@ -339,6 +339,14 @@ int mrg_gen_ffn(int B, int N, const float* a, const float* r, const float* ga, c
                 const float* w1, const float* b1, const float* w2, const float* b2, float* out, float* pred,
                 long pred_bs, float* ms_next, const float* ms_src, const unsigned char* mask, int t,
                 hipStream_t stream);
+/* The audio integrator's attention of one frame at r audio frames per prediction frame (1 <= r <= 16;
+ * MultiModalAttentionBlockSequential, multi_modal_att.py:22-31, one query, no mask: generation zeroes
+ * the padding and the block-causal rule admits all r keys): q [B][256] the projected query rows (bias
+ * added), k / v [B][r][256] the frame's projected keys / values, heads in {4, 8, 16} (D = 256 / heads);
+ * ctx [B][256] = sum_j softmax_j(q_h . k_hj / sqrt(D)) v_hj, heads concatenated (before out_proj).
+ * The row maximum is subtracted before exp; r = 1 gives ctx = v bitwise.  B = 0 launches nothing.   */
+int mrg_gen_attention(int B, int r, int heads, const float* q, const float* k, const float* v, float* ctx,
+                      hipStream_t stream);
 /* The whole frame loop in ONE persistent launch (gen.hip gen_loop_kernel): groups of 8 batch rows,
  * 16 workgroups per group exchanging each stage's outputs as {tag, value} granules; the same stages
  * as the three entries above.  ptrs: host array of 31 nb + 6 device pointers -- per block w_ih,

@@ -172,6 +172,7 @@ SIGNATURES = {
     "mrg_gen_linear": (c_int, [c_int, c_int, PP, PP, PP, PP, c_long, PP, PP, PP, c_float, P, c_long, PP, PP, P,
                                c_long, P]),
     "mrg_gen_ffn": (c_int, [c_int, c_int, P, P, P, P, c_float, P, P, P, P, P, P, c_long, P, P, P, c_int, P]),
+    "mrg_gen_attention": (c_int, [c_int, c_int, c_int, P, P, P, P, P]),
     "mrg_gen_loop_ring_bytes": (c_long, [c_int]),
     "mrg_gen_loop_fits": (c_int, [c_int, c_int]),
     "mrg_gen_loop_debug_stamps": (c_int, [P]),

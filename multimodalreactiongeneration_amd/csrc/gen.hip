@@ -23,6 +23,16 @@
 // columns per workgroup; the LayerNorms a stage consumes are recomputed from their inputs in the
 // workgroup's prologue (16 rows x 256, L2-resident) instead of a launch of their own, and each
 // workgroup writes its share of the normalised rows the next stage needs as a residual.
+//
+// At r > 1 audio frames per prediction frame (1 < r <= 16) the audio integrator's query sees r keys,
+// so its attention output depends on the query and stays in the frame loop; its keys and values
+// (the audio encoder's output through W_k / W_v) are still hoisted.  Three launches then sit between
+// the second and the third above, eight per block:
+//
+//   gen_linear     Q = LN(Z + Y) W_q^T + b_q                            (mode 0 again, rows not kept)
+//   gen_attention  ctx = softmax(Q_h K_h^T / sqrt(D)) V_h per head over the frame's r keys
+//   (few-row GEMM) a_0 = ctx W_o^T + b_o, the a_0 of the two-integrator launch
+//
 // Products on v_mfma_f32_16x16x4_f32 (exact fp32 multiply-adds; the k order differs from the
 // training kernels', fp32 class).  E = 256, FeedForward bottleneck 64 (the lstmformer config).
 #include "gen_loop.h"
@@ -345,6 +355,63 @@ __global__ __launch_bounds__(256) void gen_ffn_kernel(GenFfnArgs p) {
     const long i = (long)b * p.N + ocol;
     p.ms_next[i] = p.mask[p.t] ? y : p.ms_src[i];
   }
+}
+
+// ------------------------------------------------------------------ one query over a frame's r keys
+// The audio integrator at r > 1 audio frames per prediction frame: ctx[b][h D + d] =
+// sum_j softmax_j(q_h . k_hj / sqrt(D)) v_hj[d], no mask (every key of the frame is visible).
+// grid (B): one workgroup per batch row, thread c owns column c, so the D lanes of a head are
+// neighbours in one wave: a score is a DPP sum over 16 lanes (+ one or two cross-row shuffles at
+// D = 32 / 64), every lane of the head ends with the same r scores in registers and weighs its own
+// column of V.  Keys past r are loaded from key r - 1 (in bounds, no branch around a load) and
+// weigh 0.  r = 1: exp(s - s) = 1 and 1 / 1 = 1, so ctx = v bitwise.
+struct GenAttArgs {
+  int B, r;
+  const float* q;                // [B][GE]
+  const float* k;                // [B][r][GE]
+  const float* v;                // [B][r][GE]
+  float* ctx;                    // [B][GE]
+  float scale;                   // 1 / sqrt(D)
+};
+
+template <int D>
+__device__ __forceinline__ float gen_head_sum(float x) {
+  float s = group_sum<16>(x);
+  if (D >= 32) s += __shfl_xor(s, 16);
+  if (D >= 64) s += __shfl_xor(s, 32);
+  return s;
+}
+
+template <int D, int RMAX>
+__global__ __launch_bounds__(256) void gen_attention_kernel(GenAttArgs p) {
+  const int b = blockIdx.x, c = threadIdx.x;
+  if (b >= p.B) return;
+  const float* kb = p.k + (long)b * p.r * GE + c;
+  const float* vb = p.v + (long)b * p.r * GE + c;
+  const float q = p.q[(long)b * GE + c];
+  float kk[RMAX], vv[RMAX];
+#pragma unroll
+  for (int j = 0; j < RMAX; ++j) {
+    const int jj = min(j, p.r - 1);
+    kk[j] = kb[(long)jj * GE];
+    vv[j] = vb[(long)jj * GE];
+  }
+  float s[RMAX];
+  float m = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < RMAX; ++j) {
+    s[j] = gen_head_sum<D>(q * kk[j]) * p.scale;
+    m = fmaxf(m, s[j]);   // keys past r repeat key r - 1: the maximum is that of the r keys
+  }
+  float e = __expf(s[0] - m);
+  float sum = e, acc = e * vv[0];
+#pragma unroll
+  for (int j = 1; j < RMAX; ++j) {
+    e = j < p.r ? __expf(s[j] - m) : 0.0f;
+    sum += e;
+    acc = fmaf(e, vv[j], acc);
+  }
+  p.ctx[(long)b * GE + c] = acc / sum;
 }
 
 
@@ -718,6 +785,31 @@ MRG_API int mrg_gen_ffn(int B, int N, const float* a, const float* r, const floa
   else if (pred) klaunch(gen_ffn_kernel<0, 1>, grid, 256, 0, stream, p);
   else klaunch(gen_ffn_kernel<0, 0>, grid, 256, 0, stream, p);
   return check_launch("gen_ffn_kernel");
+}
+
+// ctx [B][256] = the attention of one query row q [B][256] (projected, bias added) over this frame's r
+// projected keys / values k, v [B][r][256], `heads` heads of D = 256 / heads in {16, 32, 64}
+// concatenated, scores scaled by 1 / sqrt(D), no mask; 1 <= r <= 16.
+MRG_API int mrg_gen_attention(int B, int r, int heads, const float* q, const float* k, const float* v, float* ctx,
+                              hipStream_t stream) {
+  MRG_REQUIRE(B >= 0 && r >= 1 && r <= 16, "mrg_gen_attention: B >= 0 and 1 <= r <= 16 (B=%d r=%d)", B, r);
+  MRG_REQUIRE(heads == 4 || heads == 8 || heads == 16, "mrg_gen_attention: heads must be 4, 8 or 16 (heads=%d)", heads);
+  if (B == 0) return 0;
+  MRG_REQUIRE(q && k && v && ctx, "mrg_gen_attention: null buffer");
+  const int D = GE / heads;
+  GenAttArgs p{B, r, q, k, v, ctx, 1.0f / sqrtf((float)D)};
+  const dim3 grid(B);
+#define MRG_GEN_ATT(DD)                                                                   \
+  do {                                                                                    \
+    if (r <= 4) klaunch(gen_attention_kernel<DD, 4>, grid, 256, 0, stream, p);            \
+    else if (r <= 8) klaunch(gen_attention_kernel<DD, 8>, grid, 256, 0, stream, p);       \
+    else klaunch(gen_attention_kernel<DD, 16>, grid, 256, 0, stream, p);                  \
+  } while (0)
+  if (D == 64) MRG_GEN_ATT(64);
+  else if (D == 32) MRG_GEN_ATT(32);
+  else MRG_GEN_ATT(16);
+#undef MRG_GEN_ATT
+  return check_launch("gen_attention_kernel");
 }
 
 static unsigned long long* g_gen_stamps = nullptr;

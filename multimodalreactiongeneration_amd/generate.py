@@ -13,13 +13,20 @@ depend on the previous frame:
 * with one audio frame per prediction frame (ratio 1), each block's integrator attention output:
   the query sees exactly one key (generation zeroes the -100 padding, so no key is ever masked, and
   the block-causal rule admits key 0 for query 0), so the softmax weight is exactly 1 and
-  MHA(q, kv) = out_proj(V(kv)) for any q -- two more [T * B]-row GEMMs per integrator.
+  MHA(q, kv) = out_proj(V(kv)) for any q -- two more [T * B]-row GEMMs per integrator;
+* with r audio frames per prediction frame (1 < ratio <= 16) the audio encoder is a zero-state LSTM
+  over the r steps of each of the [T * B] frames, and the audio integrator's query sees r keys: its
+  output depends on the query, so only its key and value projections are hoisted ([T * B * r]-row
+  GEMMs).  The partner-motion integrator still sees one key and stays hoisted as above.
 
 The frame loop then runs the main chain only: five gen.hip launches per block and one for the
-output FeedForward with the sampling select (6 x 5 + 1 = 26 per frame instead of ~145), every
-LayerNorm computed in the prologue of the launch that consumes it.  Forms outside this plan (ratio
-> 1, widths other than E = 256 / bottleneck 64, GRU mixers, grad enabled) return None and the caller
-runs the per-frame module forward.
+output FeedForward with the sampling select (5 x 5 + 1 = 26 per frame instead of ~145), every
+LayerNorm computed in the prologue of the launch that consumes it.  At ratio > 1 a block takes three
+more (the query projection, mrg_gen_attention over the frame's r keys, the output projection):
+8 x 5 + 1 = 41 per frame, launch form only (the persistent loop is a ratio-1 path).  Forms outside
+this plan (ratio > 16, integrator head widths other than 16 / 32 / 64 at ratio > 1, widths other
+than E = 256 / bottleneck 64, GRU mixers, grad enabled) return None and the caller runs the
+per-frame module forward.
 """
 from __future__ import annotations
 
@@ -40,6 +47,8 @@ E_GEN, HB_GEN = 256, 64
 # the whole frame loop as ONE persistent launch (gen.hip gen_loop_kernel) when its grid fits;
 # MRG_GEN_LOOP=0 keeps the 26 launches per frame
 _LOOP = [os.environ.get("MRG_GEN_LOOP", "1") == "1"]
+# what mrg_gen_attention takes: keys per query, and head counts (D = 256 / heads in {64, 32, 16})
+RATIO_MAX, ATT_HEADS = 16, (4, 8, 16)
 
 
 def _arr(*ts):
@@ -51,7 +60,7 @@ class GenPlan:
 
     def __init__(self, mf, ratio: int):
         self.ok = False
-        if ratio != 1 or mf.interlayer_residual or mf.repeat_with_encoder or mf.hidden_dim != E_GEN:
+        if not (1 <= ratio <= RATIO_MAX) or mf.interlayer_residual or mf.repeat_with_encoder or mf.hidden_dim != E_GEN:
             return
         if not mf._fast_eligible():
             return
@@ -61,6 +70,7 @@ class GenPlan:
             return
         layers0, eps = first
         self.eps = eps
+        self.ratio = ratio
         self.enc = layers0[1:]                   # block 0's audio / partner-motion stacks ([LstmBlock] each)
         self.fe = list(mf.feature_embedding)
         if any(e.bias is None for e in self.fe) or not self.fe[0].weight.is_cuda:
@@ -77,11 +87,13 @@ class GenPlan:
             integ = forms.integrator_form(blk.integrator) if (blk.integrator.use_fused and _FUSED_MIN_T == 1) else None
             if integ is None or len(integ.integrators) != 2 or integ.eps != eps or integ.cat_w.shape[0] != E_GEN:
                 return
+            if ratio > 1 and integ.heads not in ATT_HEADS:
+                return
             ffn = forms.relu_ffn_form(blk.feedforward, True)
             if ffn is None or ffn.w1.shape[0] != HB_GEN or ffn.ln.eps != eps:
                 return
             self.blocks.append({"lstm": main[0], "integ": integ.integrators, "cat": (integ.cat_w, integ.cat_b),
-                                "ffn": ffn})
+                                "ffn": ffn, "heads": integ.heads})
         out = forms.relu_ffn_form(mf.output_feedforward, False)
         if out is None or out.w1.shape[0] != HB_GEN or out.w2.shape[0] > 16:
             return
@@ -106,20 +118,48 @@ class GenPlan:
             x = Fn.residual_layernorm(Fn.linear(y, lay.ff_w, lay.ff_b), y, lay.ln2_w, lay.ln2_b, self.eps)
         return x
 
+    def _encoder_steps(self, x, layers, r):
+        """The audio stack at r > 1 steps per frame: x [N * r, E], N = T * B sequences of r steps, each
+        LstmBlock a zero-initial-state LSTM over the r steps (W_hh matters here), then LN1, the Linear
+        and LN2 on all N * r rows."""
+        N, H = x.shape[0] // r, E_GEN
+        # The recurrence is one persistent launch whose whole grid must be resident: at H = 256 eight
+        # workgroups serve at most 16 sequences (lstm.hip launch_fwd, lstm_mx.hip), one workgroup per
+        # CU, so a launch takes 16 * (CUs / 8) sequences (512 on 256 CUs) and N goes through in chunks
+        limit = 16 * max(1, _lib.cu_count(x.device.index or 0) // 8)
+        for lay in layers:
+            x3 = x.view(N, r, H)
+            hs = [Fn.lstm_layer(x3[i:i + limit], lay.w_ih, lay.w_hh, lay.b_ih, lay.b_hh)[0]
+                  for i in range(0, N, limit)]
+            h = (hs[0] if len(hs) == 1 else torch.cat(hs)).view(N * r, H)
+            y = Fn.residual_layernorm(h, x, lay.ln1_w, lay.ln1_b, self.eps)
+            x = Fn.residual_layernorm(Fn.linear(y, lay.ff_w, lay.ff_b), y, lay.ln2_w, lay.ln2_b, self.eps)
+        return x
+
     def generate(self, fb, mp, ms, mask):
-        """fb [T][B][1][Fa], mp / ms [T][B][1][fm] (time-major, padding zeroed), mask [T] bool ->
-        prediction [B, T, fm]."""
+        """fb [T][B][r][Fa], mp / ms [T][B][1][fm] (time-major, padding zeroed), mask [T] bool ->
+        prediction [B, T, fm].
+
+        At ratio r > 1 every block keeps the audio integrator's hoisted keys and values, [T][B][r][256]
+        each (frame t's [B][r][256] slab contiguous): 157 MB per tensor at B = 64, T = 300, r = 8, so
+        2 x 5 x 157 MB over the five blocks."""
         lib = _lib.load()
-        T, B = ms.shape[0], ms.shape[1]
+        T, B, r = ms.shape[0], ms.shape[1], self.ratio
         dev = ms.device
         E, eps = E_GEN, self.eps
-        others = [self._encoder(Fn.linear(x.reshape(T * B, -1), e.weight, e.bias), layers)
-                  for x, e, layers in zip((fb, mp), self.fe[1:], self.enc)]
-        # per block and integrator: out_proj(V(kv)), the attention output at one visible key
-        att = []
+        fa = Fn.linear(fb.reshape(T * B * r, -1), self.fe[1].weight, self.fe[1].bias)
+        others = [self._encoder(fa, self.enc[0]) if r == 1 else self._encoder_steps(fa, self.enc[0], r),
+                  self._encoder(Fn.linear(mp.reshape(T * B, -1), self.fe[2].weight, self.fe[2].bias), self.enc[1])]
+        # per block and integrator: out_proj(V(kv)), the attention output at one visible key; at r > 1
+        # the audio integrator's K(kv) and V(kv) instead, rows in [T][B][r] order
+        att, kvs = [], []
         for blk in self.blocks:
             att.append([Fn.linear(Fn.linear(kv, ip.in_w[2 * E:], ip.in_b[2 * E:]), ip.out_w, ip.out_b)
-                        for kv, ip in zip(others, blk["integ"])])
+                        if (r == 1 or i == 1) else None for i, (kv, ip) in enumerate(zip(others, blk["integ"]))])
+            if r > 1:
+                ip = blk["integ"][0]
+                kvs.append((Fn.linear(others[0], ip.in_w[E:2 * E], ip.in_b[E:2 * E]),
+                            Fn.linear(others[0], ip.in_w[2 * E:], ip.in_b[2 * E:])))
         msc = ms.reshape(T, B, self.fm).contiguous()
         # the kernel reads one byte per frame (a device bool tensor as it is: refreshed per graph replay)
         mask_u8 = mask if (mask.device == dev and mask.dtype in (torch.bool, torch.uint8)) \
@@ -130,8 +170,11 @@ class GenPlan:
         y01, z01 = (torch.empty(B, 2 * E, device=dev, dtype=F32) for _ in range(2))
         st = _stream()
         fe0 = self.fe[0]
-        if _LOOP[0] and lib.mrg_gen_loop_fits(B, _lib.cu_count(dev.index or 0)) == 1:
+        # (the persistent loop hoists both integrators' outputs: a ratio-1 path)
+        if r == 1 and _LOOP[0] and lib.mrg_gen_loop_fits(B, _lib.cu_count(dev.index or 0)) == 1:
             return self._generate_loop(lib, B, T, att, msc, mask_u8, pred, st)
+        if r > 1:
+            qb, cx, a0 = (torch.empty(B, E, device=dev, dtype=F32) for _ in range(3))
         # argument tuples made once (the frame loop only varies the frame pointers)
         calls = []
         for bi, blk in enumerate(self.blocks):
@@ -144,6 +187,8 @@ class GenPlan:
                       _arr(i0.ln1_b, i1.ln1_b), _arr(i0.ff_w, i1.ff_w), _arr(i0.ff_b, i1.ff_b)),
                 lin2=(_arr(_ptr(z01), _ptr(z01, E)), _arr(_ptr(y01), _ptr(y01, E)), _arr(i0.ln2_w, i1.ln2_w),
                       _arr(i0.ln2_b, i1.ln2_b), _arr(cw), _arr(cb)),
+                # r > 1: the audio integrator's query projection (in_w's first E rows) and out_proj
+                linq=(_arr(i0.in_w), _arr(i0.in_b)), outp=(i0.out_w, i0.out_b), heads=blk["heads"],
                 ffn=ffn[:4]))
         out = self.out
         lastln = self.blocks[-1]["ffn"].ln
@@ -151,6 +196,7 @@ class GenPlan:
         f_lstm, f_lin0 = 2.0 * B * 4 * E * E, 2.0 * B * E * E
         f_lin1, f_lin2 = 2.0 * B * 2 * E * E, 2.0 * B * E * 2 * E
         f_ffn, f_out = 2.0 * B * HB_GEN * (E + E), 2.0 * B * HB_GEN * (E + self.fm)
+        f_att = 2.0 * B * r * 2 * E    # q . k and p v over the frame's r keys, all heads
         for t in range(T):
             for bi, c in enumerate(calls):
                 w_ih, b_ih, b_hh, prev = c["lstm"]
@@ -165,18 +211,34 @@ class GenPlan:
                         _lib.check(lib.mrg_gen_lstm(B, self.fm, None, None, None, _ptr(zf), _ptr(m3),
                                                     _ptr(prev.weight), _ptr(prev.bias), eps, _ptr(xb), _ptr(w_ih),
                                                     _ptr(b_ih), _ptr(b_hh), _ptr(hh), st), "gen lstm")
-                a, r, ga, be, w, bias = c["lin0"]
+                a, rs, ga, be, w, bias = c["lin0"]
                 with _probe("gen", f_lin0):
-                    _lib.check(lib.mrg_gen_linear(0, B, a, r, ga, be, E, None, None, None, eps, _ptr(y), E, w, bias,
+                    _lib.check(lib.mrg_gen_linear(0, B, a, rs, ga, be, E, None, None, None, eps, _ptr(y), E, w, bias,
                                                   _ptr(z), E, st), "gen mixer linear")
-                a, r, ga, be, ga2, be2, w, bias = c["lin1"]
-                a2 = _arr(_ptr(att[bi][0], t * B * E), _ptr(att[bi][1], t * B * E))
+                a, rs, ga, be, ga2, be2, w, bias = c["lin1"]
+                if r == 1:
+                    a2 = _arr(_ptr(att[bi][0], t * B * E), _ptr(att[bi][1], t * B * E))
+                else:
+                    # Q = LN(Z + Y) W_q^T + b_q (the launch above's prologue again; its rows are not
+                    # kept), the attention over frame t's r keys, a_0 = ctx W_o^T + b_o
+                    wq, bq = c["linq"]
+                    with _probe("gen", f_lin0):
+                        _lib.check(lib.mrg_gen_linear(0, B, a, rs, ga, be, E, None, None, None, eps, None, 0, wq, bq,
+                                                      _ptr(qb), E, st), "gen query linear")
+                    kt, vt = kvs[bi]
+                    with _probe("gen", f_att):
+                        _lib.check(lib.mrg_gen_attention(B, r, c["heads"], _ptr(qb), _ptr(kt, t * B * r * E),
+                                                         _ptr(vt, t * B * r * E), _ptr(cx), st), "gen attention")
+                    wo, bo = c["outp"]
+                    with _probe("gen", f_lin0):
+                        Fn.gemm(B, E, E, _ptr(cx), 0, E, _ptr(wo), 1, E, _ptr(a0), E, bias=_ptr(bo), device=dev)
+                    a2 = _arr(a0, _ptr(att[bi][1], t * B * E))
                 with _probe("gen", f_lin1):
-                    _lib.check(lib.mrg_gen_linear(1, B, a, r, ga, be, E, a2, ga2, be2, eps, _ptr(y01), 2 * E, w,
+                    _lib.check(lib.mrg_gen_linear(1, B, a, rs, ga, be, E, a2, ga2, be2, eps, _ptr(y01), 2 * E, w,
                                                   bias, _ptr(z01), 2 * E, st), "gen integrators")
-                a, r, ga, be, w, bias = c["lin2"]
+                a, rs, ga, be, w, bias = c["lin2"]
                 with _probe("gen", f_lin2):
-                    _lib.check(lib.mrg_gen_linear(2, B, a, r, ga, be, 2 * E, None, None, None, eps, None, 0, w, bias,
+                    _lib.check(lib.mrg_gen_linear(2, B, a, rs, ga, be, 2 * E, None, None, None, eps, None, 0, w, bias,
                                                   _ptr(m3), E, st), "gen cat_linear")
                 w1, b1, w2, b2 = c["ffn"]
                 with _probe("gen", f_ffn):
