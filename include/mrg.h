@@ -197,7 +197,8 @@ int mrg_lstm_cell_bwd(int B, int H, const float* gates, const float* c, const fl
  * products are GEMMs (gx = x W_ih^T + b_ih for all steps, gh = h_{t-1} W_hh^T per step), the cell
  * fuses the rest.  fwd: h = (1-z) n + z h_{t-1}, saves gates (r, z, n) and ghn = gh_n + b_hn.
  * bwd: dh = dy + dh_next; writes dgx, dgh (= dgx with the n column times r) and dhp = dh z (the
- * caller's GEMM adds dgh W_hh).  hp / dy / dh_next nullable (zero).                          */
+ * caller's GEMM adds dgh W_hh).  hp / dy / dh_next nullable (zero); fwd's gh nullable (zero: the
+ * product of a zero state).                                                                  */
 int mrg_gru_cell_fwd(int B, int H, const float* gx, long gx_ld, const float* gh, const float* b_hh,
                      const float* hp, long hp_ld, float* h, long h_ld, float* gates, long g_ld, float* ghn,
                      long n_ld, hipStream_t stream);
@@ -320,6 +321,10 @@ int mrg_lstm_step_fwd(int B, int H, int In, const float* x, const float* h0, con
  * mrg_gen_lstm: X = ms W_fe^T + b_fe (ms [B][fm], fm <= 16; feature_embedding.0) or X = LN(a + r)
  *   (the previous block's FeedForward residual LayerNorm), written to xw [B][256]; gates =
  *   X W_ih^T + b_ih + b_hh, zero-state cell (LSTMMixer, mixer_block.py:237-252) -> h [B][256].
+ * mrg_gen_gru: the same two prologues into xw, then the zero-state step of a GRU mixer (torch.nn.GRU,
+ *   gates r, z, n; GRUMixer, mixer_block.py:193-208): G = X W_ih^T + b_ih (w_ih [768][256], b_ih / b_hh
+ *   [768]), r = s(G_r + b_hr), z = s(G_z + b_hz), n = tanh(G_n + r b_hn), h = (1 - z) n -> h [B][256].
+ *   h_0 = 0, so W_hh is no argument.  Exactly one prologue must be given; B = 0 launches nothing.
  * mrg_gen_linear mode 0: out = LN(a + r) W^T + b, LN rows to xw (LSTMMixerBlock, mixer_block.py:479-507);
  *   mode 1: M = LN(a + r), Y_i = LN(a2[i] + M) to xw[:, 256 i:], out[:, 256 i:] = Y_i W_i^T + b_i
  *   (both integrators' MHAMixerBlocks, mixer_block.py:567-603, with their attention output a2[i]);
@@ -331,6 +336,9 @@ int mrg_lstm_step_fwd(int B, int H, int In, const float* x, const float* h0, con
 int mrg_gen_lstm(int B, int fm, const float* ms, const float* fe_w, const float* fe_b, const float* a,
                  const float* r, const float* ga, const float* be, float eps, float* xw, const float* w_ih,
                  const float* b_ih, const float* b_hh, float* h, hipStream_t stream);
+int mrg_gen_gru(int B, int fm, const float* ms, const float* fe_w, const float* fe_b, const float* a,
+                const float* r, const float* ga, const float* be, float eps, float* xw, const float* w_ih,
+                const float* b_ih, const float* b_hh, float* h, hipStream_t stream);
 int mrg_gen_linear(int mode, int B, const float* const* a, const float* const* r, const float* const* ga,
                    const float* const* be, long lda, const float* const* a2, const float* const* ga2,
                    const float* const* be2, float eps, float* xw, long ldxw, const float* const* w,

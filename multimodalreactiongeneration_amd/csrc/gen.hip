@@ -12,6 +12,7 @@
 //
 //   gen_lstm    X = LN(ffn(prev) + prev) (block 0: X = ms_in W_fe^T + b_fe), gates = X W_ih^T + b,
 //               zero-state cell -> h                                    (mixer_block.py:237-252)
+//               (a GRU mixer: gen_gru, gates = X W_ih^T + b_ih, zero-state GRU cell, mixer_block.py:193-208)
 //   gen_linear  Y = LN(h + X), Z = Y W^T + b                           (mixer_block.py:479-507)
 //   gen_linear  M = LN(Z + Y), Y_i = LN(a_i + M), Z_i = Y_i W_i^T + b_i  (both integrators,
 //               mixer_block.py:567-603)
@@ -52,7 +53,7 @@ struct GenLstmArgs {
   const float* be;
   float eps;
   float* xw;                     // X [B][GE] (this block's residual input), each workgroup its share
-  const float* w_ih;             // [4 GE][GE]
+  const float* w_ih;             // [4 GE][GE] (gen_gru_kernel: [3 GE][GE], gates r, z, n)
   const float* b_ih;
   const float* b_hh;
   float* h;                      // [B][GE]
@@ -135,28 +136,13 @@ __device__ __forceinline__ float gen_sum(const float (*red)[GR][17], int m, int 
 // weight operands, the LayerNorm gamma / beta, the biases of its outputs), then the activation rows
 // (clamped past B, zeroed after), so a kernel waits about one memory round trip before its products.
 
-// ------------------------------------------------------------------ LSTM mixer gates + cell
-// grid (GE / 4 unit groups, ceil(B / 16)); column n of the tile = gate n >> 2 of unit 4 bx + (n & 3)
+// The recurrent mixers' input rows X [16][GE] of this workgroup into xs (rows past B zero), and its
+// share (GE / gridDim.x columns) of them into p.xw.  PRO 0: X = ms W_fe^T + b_fe; PRO 1: X = LN(a + r)
 template <int PRO>
-__global__ __launch_bounds__(256) void gen_lstm_kernel(GenLstmArgs p) {
-  constexpr int KP = GE + 4;
-  __shared__ __attribute__((aligned(16))) float xs[GR][KP];
-  __shared__ float red[4][GR][17];
-  __shared__ float msl[GR][16];
+__device__ __forceinline__ void gen_mixer_x(const GenLstmArgs& p, float (*xs)[GE + 4], float (*msl)[16]) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int row0 = blockIdx.y * GR, u0 = 4 * blockIdx.x;
+  const int row0 = blockIdx.y * GR;
   const int share = GE / gridDim.x;   // X columns this workgroup writes back
-  const int n = lane & 15;
-  float4 w[GE / 4 / 16];
-  gen_wload<GE / 4>(p.w_ih + (long)((n >> 2) * GE + u0 + (n & 3)) * GE, wave * (GE / 4), lane, w);
-  // cell thread (m, j): its unit's biases
-  const int cm = tid >> 2, cj = tid & 3, cu = u0 + cj;
-  float bi = 0.f, bg = 0.f, bo = 0.f;
-  if (tid < 4 * GR) {
-    bi = p.b_ih[cu] + p.b_hh[cu];
-    bg = p.b_ih[2 * GE + cu] + p.b_hh[2 * GE + cu];
-    bo = p.b_ih[3 * GE + cu] + p.b_hh[3 * GE + cu];
-  }
   if (PRO == 0) {
     // X = ms W_fe^T + b_fe (K = fm <= 16): the 16 rows' inputs staged in LDS, thread = column
     const int k = tid;
@@ -199,6 +185,30 @@ __global__ __launch_bounds__(256) void gen_lstm_kernel(GenLstmArgs p) {
       *reinterpret_cast<float4*>(&xs[m][k]) = v;
     }
   }
+}
+
+// ------------------------------------------------------------------ LSTM mixer gates + cell
+// grid (GE / 4 unit groups, ceil(B / 16)); column n of the tile = gate n >> 2 of unit 4 bx + (n & 3)
+template <int PRO>
+__global__ __launch_bounds__(256) void gen_lstm_kernel(GenLstmArgs p) {
+  constexpr int KP = GE + 4;
+  __shared__ __attribute__((aligned(16))) float xs[GR][KP];
+  __shared__ float red[4][GR][17];
+  __shared__ float msl[GR][16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row0 = blockIdx.y * GR, u0 = 4 * blockIdx.x;
+  const int n = lane & 15;
+  float4 w[GE / 4 / 16];
+  gen_wload<GE / 4>(p.w_ih + (long)((n >> 2) * GE + u0 + (n & 3)) * GE, wave * (GE / 4), lane, w);
+  // cell thread (m, j): its unit's biases
+  const int cm = tid >> 2, cj = tid & 3, cu = u0 + cj;
+  float bi = 0.f, bg = 0.f, bo = 0.f;
+  if (tid < 4 * GR) {
+    bi = p.b_ih[cu] + p.b_hh[cu];
+    bg = p.b_ih[2 * GE + cu] + p.b_hh[2 * GE + cu];
+    bo = p.b_ih[3 * GE + cu] + p.b_hh[3 * GE + cu];
+  }
+  gen_mixer_x<PRO>(p, xs, msl);
   __syncthreads();
   gv4 acc = gv4{0.f, 0.f, 0.f, 0.f};
   acc = gen_mfma<KP, GE / 4>(&xs[0][0], w, wave * (GE / 4), lane, acc);
@@ -210,6 +220,44 @@ __global__ __launch_bounds__(256) void gen_lstm_kernel(GenLstmArgs p) {
     const float zo = gen_sum(red, cm, 12 + cj) + bo;
     const float c = sigmoidf_(zi) * tanhf_(zg);   // f c0 + i g with c0 = 0
     p.h[(long)(row0 + cm) * GE + cu] = sigmoidf_(zo) * tanhf_(c);
+  }
+}
+
+// ------------------------------------------------------------------ GRU mixer gates + cell
+// The zero-state step of torch.nn.GRU (gates r, z, n): h_0 = 0, so W_hh is never read and
+// h = (1 - z) n with r = s(G_r + b_hr), z = s(G_z + b_hz), n = tanh(G_n + r b_hn), G = X W_ih^T + b_ih
+// (the sums in mrg_gru_cell_fwd's order).  grid (GE / 16 unit groups, ceil(B / 16)): tile g of the
+// workgroup is gate g of units 16 bx .. 16 bx + 15, weight rows g GE + 16 bx + n.
+template <int PRO>
+__global__ __launch_bounds__(256) void gen_gru_kernel(GenLstmArgs p) {
+  constexpr int KP = GE + 4;
+  __shared__ __attribute__((aligned(16))) float xs[GR][KP];
+  __shared__ float red[3][4][GR][17];
+  __shared__ float msl[GR][16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row0 = blockIdx.y * GR, u0 = 16 * blockIdx.x;
+  float4 w[3][GE / 4 / 16];
+#pragma unroll
+  for (int g = 0; g < 3; ++g)
+    gen_wload<GE / 4>(p.w_ih + (long)(g * GE + u0 + (lane & 15)) * GE, wave * (GE / 4), lane, w[g]);
+  // cell thread (m, j): its unit's biases
+  const int cm = tid >> 4, cj = tid & 15, cu = u0 + cj;
+  const float bir = p.b_ih[cu], biz = p.b_ih[GE + cu], bin = p.b_ih[2 * GE + cu];
+  const float bhr = p.b_hh[cu], bhz = p.b_hh[GE + cu], bhn = p.b_hh[2 * GE + cu];
+  gen_mixer_x<PRO>(p, xs, msl);
+  __syncthreads();
+#pragma unroll
+  for (int g = 0; g < 3; ++g) {
+    gv4 acc = gv4{0.f, 0.f, 0.f, 0.f};
+    acc = gen_mfma<KP, GE / 4>(&xs[0][0], w[g], wave * (GE / 4), lane, acc);
+    gen_park(red[g], wave, lane, acc);
+  }
+  __syncthreads();
+  if (row0 + cm < p.B) {
+    const float rg = sigmoidf_((gen_sum(red[0], cm, cj) + bir) + bhr);
+    const float zg = sigmoidf_((gen_sum(red[1], cm, cj) + biz) + bhz);
+    const float ng = tanhf_((gen_sum(red[2], cm, cj) + bin) + rg * bhn);
+    p.h[(long)(row0 + cm) * GE + cu] = (1.0f - zg) * ng;   // + z h_0 with h_0 = 0
   }
 }
 
@@ -733,6 +781,23 @@ MRG_API int mrg_gen_lstm(int B, int fm, const float* ms, const float* fe_w, cons
   if (ms) klaunch(gen_lstm_kernel<0>, grid, 256, 0, stream, p);
   else klaunch(gen_lstm_kernel<1>, grid, 256, 0, stream, p);
   return check_launch("gen_lstm_kernel");
+}
+
+// The GRU mixer's form of mrg_gen_lstm: the same two prologues into xw [B][256], then the zero-state
+// torch.nn.GRU step (gates r, z, n; w_ih [768][256], b_ih / b_hh [768]; W_hh is not read) -> h [B][256].
+MRG_API int mrg_gen_gru(int B, int fm, const float* ms, const float* fe_w, const float* fe_b, const float* a,
+                        const float* r, const float* ga, const float* be, float eps, float* xw, const float* w_ih,
+                        const float* b_ih, const float* b_hh, float* h, hipStream_t stream) {
+  if (B == 0) return 0;
+  MRG_REQUIRE(B > 0 && xw && w_ih && b_ih && b_hh && h, "mrg_gen_gru: B >= 0 and xw / w_ih / b_ih / b_hh / h (B=%d)", B);
+  MRG_REQUIRE(!(ms && (a || r || ga || be)), "mrg_gen_gru: give ms or the LayerNorm inputs, not both");
+  MRG_REQUIRE(ms ? (fm >= 1 && fm <= 16 && fe_w && fe_b) : (a && r && ga && be),
+              "mrg_gen_gru: give ms + feature embedding (fm <= 16) or the LayerNorm inputs (fm=%d)", fm);
+  GenLstmArgs p{B, fm, ms, fe_w, fe_b, a, r, ga, be, eps, xw, w_ih, b_ih, b_hh, h};
+  const dim3 grid(GE / 16, gen_rows(B));
+  if (ms) klaunch(gen_gru_kernel<0>, grid, 256, 0, stream, p);
+  else klaunch(gen_gru_kernel<1>, grid, 256, 0, stream, p);
+  return check_launch("gen_gru_kernel");
 }
 
 // mode 0: out [B][256] = LN(a + r) W^T + b, the normalised rows into xw [B][256]

@@ -9,8 +9,8 @@
 
 namespace mrg {
 
-// gx rows of stride gx_ld ([B, 3H] slice of step t), gh [B, 3H] dense, hp rows of stride hp_ld
-// (nullable: zero state); writes h (stride h_ld), gates [B, 3H] (r, z, n) and ghn [B, H] (stride sv_ld
+// gx rows of stride gx_ld ([B, 3H] slice of step t), gh [B, 3H] dense (nullable: zero, the product of a
+// zero state), hp rows of stride hp_ld (nullable: zero state); writes h (stride h_ld), gates [B, 3H] (r, z, n) and ghn [B, H] (stride sv_ld
 // rows for both, i.e. the step-t slices of [B, T, .] buffers)
 __global__ __launch_bounds__(256) void gru_cell_fwd_kernel(int B, int H, const float* __restrict__ gx, long gx_ld,
                                                            const float* __restrict__ gh, const float* __restrict__ b_hh,
@@ -22,10 +22,14 @@ __global__ __launch_bounds__(256) void gru_cell_fwd_kernel(int B, int H, const f
   if (i >= (long)B * H) return;
   const int b = i / H, u = i % H;
   const float* x = gx + (long)b * gx_ld;
-  const float* g = gh + (long)b * 3 * H;
-  const float r = sigmoidf_(x[u] + g[u] + b_hh[u]);
-  const float z = sigmoidf_(x[H + u] + g[H + u] + b_hh[H + u]);
-  const float hn = g[2 * H + u] + b_hh[2 * H + u];
+  float gr = 0.0f, gz = 0.0f, gn = 0.0f;
+  if (gh) {
+    const float* g = gh + (long)b * 3 * H;
+    gr = g[u]; gz = g[H + u]; gn = g[2 * H + u];
+  }
+  const float r = sigmoidf_(x[u] + gr + b_hh[u]);
+  const float z = sigmoidf_(x[H + u] + gz + b_hh[H + u]);
+  const float hn = gn + b_hh[2 * H + u];
   const float n = tanhf_(x[2 * H + u] + r * hn);
   const float hprev = hp ? hp[(long)b * hp_ld + u] : 0.0f;
   h[(long)b * h_ld + u] = (1.0f - z) * n + z * hprev;

@@ -8,14 +8,14 @@ frame's self-motion input is the previous prediction (mask true) or motion_s one
 What this module hoists out of the frame loop (inference only, no autograd), because it does not
 depend on the previous frame:
 
-* the other modalities' block-0 encoders (feature Linear + every LSTM mixer block of the audio and
-  partner-motion stacks), as [T * B]-row GEMMs, zero-state LSTM cells and LayerNorms;
+* the other modalities' block-0 encoders (feature Linear + every LSTM or GRU mixer block of the audio
+  and partner-motion stacks), as [T * B]-row GEMMs, zero-state LSTM / GRU cells and LayerNorms;
 * with one audio frame per prediction frame (ratio 1), each block's integrator attention output:
   the query sees exactly one key (generation zeroes the -100 padding, so no key is ever masked, and
   the block-causal rule admits key 0 for query 0), so the softmax weight is exactly 1 and
   MHA(q, kv) = out_proj(V(kv)) for any q -- two more [T * B]-row GEMMs per integrator;
 * with r audio frames per prediction frame (1 < ratio <= 16) the audio encoder is a zero-state LSTM
-  over the r steps of each of the [T * B] frames, and the audio integrator's query sees r keys: its
+  or GRU over the r steps of each of the [T * B] frames, and the audio integrator's query sees r keys: its
   output depends on the query, so only its key and value projections are hoisted ([T * B * r]-row
   GEMMs).  The partner-motion integrator still sees one key and stays hoisted as above.
 
@@ -23,10 +23,18 @@ The frame loop then runs the main chain only: five gen.hip launches per block an
 output FeedForward with the sampling select (5 x 5 + 1 = 26 per frame instead of ~145), every
 LayerNorm computed in the prologue of the launch that consumes it.  At ratio > 1 a block takes three
 more (the query projection, mrg_gen_attention over the frame's r keys, the output projection):
-8 x 5 + 1 = 41 per frame, launch form only (the persistent loop is a ratio-1 path).  Forms outside
-this plan (ratio > 16, integrator head widths other than 16 / 32 / 64 at ratio > 1, widths other
-than E = 256 / bottleneck 64, GRU mixers, grad enabled) return None and the caller runs the
-per-frame module forward.
+8 x 5 + 1 = 41 per frame, launch form only (the persistent loop is a ratio-1 path).
+
+Each modality's embedding mixer is an LSTM or a GRU (config.yaml / config_gru.yaml, and any mix of the
+two).  Only the recurrent cell of the frame chain knows which: a GRU main chain runs mrg_gen_gru where
+the LSTM runs mrg_gen_lstm (the zero-state torch.nn.GRU step, which never reads W_hh), the same
+launch counts.  The persistent loop's first stage is the LSTM cell, so it serves LSTM main chains
+only, whatever the side stacks are (it reads their hoisted attention outputs); a GRU main chain at
+ratio 1 runs the 26 launches.
+
+Forms outside this plan (ratio > 16, integrator head widths other than 16 / 32 / 64 at ratio > 1,
+widths other than E = 256 / bottleneck 64, mixers other than one-layer unidirectional LSTM / GRU
+blocks, grad enabled) return None and the caller runs the per-frame module forward.
 """
 from __future__ import annotations
 
@@ -62,25 +70,28 @@ class GenPlan:
         self.ok = False
         if not (1 <= ratio <= RATIO_MAX) or mf.interlayer_residual or mf.repeat_with_encoder or mf.hidden_dim != E_GEN:
             return
-        if not mf._fast_eligible():
+        # (not _fast_eligible: that is the training schedules' predicate and takes LSTM embeddings only;
+        # here every embedding is an LSTM or a GRU chain, forms.embedding_mixer_form below)
+        if mf._module_path_only():
             return
         blocks = list(mf.metaformer_blocks)
-        first = forms.embedding_stack_form(blocks[0])
+        first = forms.embedding_mixer_form(blocks[0])
         if first is None or len(first[0]) != 3:
             return
         layers0, eps = first
         self.eps = eps
         self.ratio = ratio
-        self.enc = layers0[1:]                   # block 0's audio / partner-motion stacks ([LstmBlock] each)
+        # block 0's audio / partner-motion stacks: ("lstm", [LstmBlock]) or ("gru", [GruBlock]) each
+        self.enc = layers0[1:]
         self.fe = list(mf.feature_embedding)
         if any(e.bias is None for e in self.fe) or not self.fe[0].weight.is_cuda:
             return
         self.blocks = []
         for bi, blk in enumerate(blocks):
-            got = forms.embedding_stack_form(blk) if bi else first
+            got = forms.embedding_mixer_form(blk) if bi else first
             if got is None:
                 return
-            (main, *_others), blk_eps = got          # the main modality's chain: one LstmBlock per block
+            ((kind, main), *_others), blk_eps = got   # the main modality's chain: one Lstm- / GruBlock per block
             if len(main) != 1 or blk_eps != eps or any(v is None for v in main[0]):
                 return
             # the frames are T = 1 calls of the fused integrator: its switches hold here too
@@ -92,8 +103,8 @@ class GenPlan:
             ffn = forms.relu_ffn_form(blk.feedforward, True)
             if ffn is None or ffn.w1.shape[0] != HB_GEN or ffn.ln.eps != eps:
                 return
-            self.blocks.append({"lstm": main[0], "integ": integ.integrators, "cat": (integ.cat_w, integ.cat_b),
-                                "ffn": ffn, "heads": integ.heads})
+            self.blocks.append({"kind": kind, "mix": main[0], "integ": integ.integrators,
+                                "cat": (integ.cat_w, integ.cat_b), "ffn": ffn, "heads": integ.heads})
         out = forms.relu_ffn_form(mf.output_feedforward, False)
         if out is None or out.w1.shape[0] != HB_GEN or out.w2.shape[0] > 16:
             return
@@ -101,35 +112,55 @@ class GenPlan:
         self.fm = out.w2.shape[0]
         if self.fe[0].weight.shape[1] != self.fm:
             return
+        # the persistent loop's first stage is the LSTM cell
+        self.loop_form = all(b["kind"] == "lstm" for b in self.blocks)
         self.ok = True
 
     # ---- frame-independent work over all T frames ([T * B] rows, time-major)
-    def _encoder(self, x, layers):
+    def _encoder(self, x, stack):
+        kind, layers = stack
         lib = _lib.load()
         N, H = x.shape[0], E_GEN
-        gates = torch.empty(N, 4 * H, device=x.device, dtype=F32)
-        c = torch.empty(N, H, device=x.device, dtype=F32)
+        ng = 4 if kind == "lstm" else 3
+        gates = torch.empty(N, ng * H, device=x.device, dtype=F32)
+        c = torch.empty(N, H, device=x.device, dtype=F32)   # the LSTM's cell state; the GRU cell's gh_n + b_hn
         for lay in layers:
             g = Fn.linear(x, lay.w_ih, lay.b_ih)
             h = torch.empty(N, H, device=x.device, dtype=F32)
-            _lib.check(lib.mrg_lstm_cell_fwd(N, H, _ptr(g), 4 * H, _ptr(lay.b_hh), None, _ptr(gates), _ptr(c), _ptr(h),
-                                             H, None, _stream()), "gen encoder cell")
+            if kind == "lstm":
+                _lib.check(lib.mrg_lstm_cell_fwd(N, H, _ptr(g), 4 * H, _ptr(lay.b_hh), None, _ptr(gates), _ptr(c),
+                                                 _ptr(h), H, None, _stream()), "gen encoder cell")
+            else:
+                # zero state: no previous h and no h W_hh^T product (gh null reads as zero)
+                _lib.check(lib.mrg_gru_cell_fwd(N, H, _ptr(g), 3 * H, None, _ptr(lay.b_hh), None, H, _ptr(h), H,
+                                                _ptr(gates), 3 * H, _ptr(c), H, _stream()), "gen encoder gru cell")
             y = Fn.residual_layernorm(h, x, lay.ln1_w, lay.ln1_b, self.eps)
             x = Fn.residual_layernorm(Fn.linear(y, lay.ff_w, lay.ff_b), y, lay.ln2_w, lay.ln2_b, self.eps)
         return x
 
-    def _encoder_steps(self, x, layers, r):
+    def _encoder_steps(self, x, stack, r):
         """The audio stack at r > 1 steps per frame: x [N * r, E], N = T * B sequences of r steps, each
-        LstmBlock a zero-initial-state LSTM over the r steps (W_hh matters here), then LN1, the Linear
-        and LN2 on all N * r rows."""
+        Lstm- / GruBlock a zero-initial-state recurrence over the r steps (W_hh matters here), then LN1,
+        the Linear and LN2 on all N * r rows."""
+        kind, layers = stack
         N, H = x.shape[0] // r, E_GEN
-        # The recurrence is one persistent launch whose whole grid must be resident: at H = 256 eight
-        # workgroups serve at most 16 sequences (lstm.hip launch_fwd, lstm_mx.hip), one workgroup per
-        # CU, so a launch takes 16 * (CUs / 8) sequences (512 on 256 CUs) and N goes through in chunks
-        limit = 16 * max(1, _lib.cu_count(x.device.index or 0) // 8)
+        cus = _lib.cu_count(x.device.index or 0)
+        if kind == "lstm":
+            # The recurrence is one persistent launch whose whole grid must be resident: at H = 256 eight
+            # workgroups serve at most 16 sequences (lstm.hip launch_fwd, lstm_mx.hip), one workgroup per
+            # CU, so a launch takes 16 * (CUs / 8) sequences (512 on 256 CUs) and N goes through in chunks
+            limit = 16 * max(1, cus // 8)
+            layer = Fn.lstm_layer
+        else:
+            # The GRU's persistent launch has the same residency rule and no fallback (gru_rec.hip
+            # gru_launch_fwd returns an error when no batch tile fits): at H = 256 a ring of 4 or 8
+            # workgroups (mrg_gru_config) serves at most 8 sequences, so with one workgroup per CU and
+            # the larger ring a launch takes 8 * (CUs / 8) sequences (256 on 256 CUs); chunked likewise
+            limit = 8 * max(1, cus // 8)
+            layer = Fn.gru_layer
         for lay in layers:
             x3 = x.view(N, r, H)
-            hs = [Fn.lstm_layer(x3[i:i + limit], lay.w_ih, lay.w_hh, lay.b_ih, lay.b_hh)[0]
+            hs = [layer(x3[i:i + limit], lay.w_ih, lay.w_hh, lay.b_ih, lay.b_hh)[0]
                   for i in range(0, N, limit)]
             h = (hs[0] if len(hs) == 1 else torch.cat(hs)).view(N * r, H)
             y = Fn.residual_layernorm(h, x, lay.ln1_w, lay.ln1_b, self.eps)
@@ -170,17 +201,20 @@ class GenPlan:
         y01, z01 = (torch.empty(B, 2 * E, device=dev, dtype=F32) for _ in range(2))
         st = _stream()
         fe0 = self.fe[0]
-        # (the persistent loop hoists both integrators' outputs: a ratio-1 path)
-        if r == 1 and _LOOP[0] and lib.mrg_gen_loop_fits(B, _lib.cu_count(dev.index or 0)) == 1:
+        # (the persistent loop hoists both integrators' outputs: a ratio-1 path, LSTM main chain only)
+        if r == 1 and self.loop_form and _LOOP[0] and lib.mrg_gen_loop_fits(B, _lib.cu_count(dev.index or 0)) == 1:
             return self._generate_loop(lib, B, T, att, msc, mask_u8, pred, st)
         if r > 1:
             qb, cx, a0 = (torch.empty(B, E, device=dev, dtype=F32) for _ in range(3))
         # argument tuples made once (the frame loop only varies the frame pointers)
         calls = []
         for bi, blk in enumerate(self.blocks):
-            lstm, (i0, i1), (cw, cb), ffn = blk["lstm"], blk["integ"], blk["cat"], blk["ffn"]
+            lstm, (i0, i1), (cw, cb), ffn = blk["mix"], blk["integ"], blk["cat"], blk["ffn"]
             prev = self.blocks[bi - 1]["ffn"].ln if bi else None
             calls.append(dict(
+                # the recurrent mixer's launch: the two entries take the same arguments
+                cell=lib.mrg_gen_lstm if blk["kind"] == "lstm" else lib.mrg_gen_gru,
+                f_cell=2.0 * B * (4 if blk["kind"] == "lstm" else 3) * E * E,
                 lstm=(lstm.w_ih, lstm.b_ih, lstm.b_hh, prev),
                 lin0=(_arr(hh), _arr(xb), _arr(lstm.ln1_w), _arr(lstm.ln1_b), _arr(lstm.ff_w), _arr(lstm.ff_b)),
                 lin1=(_arr(z), _arr(y), _arr(lstm.ln2_w), _arr(lstm.ln2_b), _arr(i0.ln1_w, i1.ln1_w),
@@ -193,24 +227,25 @@ class GenPlan:
         out = self.out
         lastln = self.blocks[-1]["ffn"].ln
         # algorithmic FLOPs of each launch (2 x rows x outputs x K; the LayerNorms are O(rows x E))
-        f_lstm, f_lin0 = 2.0 * B * 4 * E * E, 2.0 * B * E * E
+        f_lin0 = 2.0 * B * E * E
         f_lin1, f_lin2 = 2.0 * B * 2 * E * E, 2.0 * B * E * 2 * E
         f_ffn, f_out = 2.0 * B * HB_GEN * (E + E), 2.0 * B * HB_GEN * (E + self.fm)
         f_att = 2.0 * B * r * 2 * E    # q . k and p v over the frame's r keys, all heads
         for t in range(T):
             for bi, c in enumerate(calls):
                 w_ih, b_ih, b_hh, prev = c["lstm"]
+                cell, f_lstm = c["cell"], c["f_cell"]
                 if bi == 0:
                     src = msc[0] if t == 0 else ms_in
                     with _probe("gen", f_lstm + 2.0 * B * E * self.fm):
-                        _lib.check(lib.mrg_gen_lstm(B, self.fm, _ptr(src), _ptr(fe0.weight), _ptr(fe0.bias), None, None,
-                                                    None, None, eps, _ptr(xb), _ptr(w_ih), _ptr(b_ih), _ptr(b_hh),
-                                                    _ptr(hh), st), "gen lstm")
+                        _lib.check(cell(B, self.fm, _ptr(src), _ptr(fe0.weight), _ptr(fe0.bias), None, None,
+                                        None, None, eps, _ptr(xb), _ptr(w_ih), _ptr(b_ih), _ptr(b_hh),
+                                        _ptr(hh), st), "gen mixer cell")
                 else:
                     with _probe("gen", f_lstm):
-                        _lib.check(lib.mrg_gen_lstm(B, self.fm, None, None, None, _ptr(zf), _ptr(m3),
-                                                    _ptr(prev.weight), _ptr(prev.bias), eps, _ptr(xb), _ptr(w_ih),
-                                                    _ptr(b_ih), _ptr(b_hh), _ptr(hh), st), "gen lstm")
+                        _lib.check(cell(B, self.fm, None, None, None, _ptr(zf), _ptr(m3),
+                                        _ptr(prev.weight), _ptr(prev.bias), eps, _ptr(xb), _ptr(w_ih),
+                                        _ptr(b_ih), _ptr(b_hh), _ptr(hh), st), "gen mixer cell")
                 a, rs, ga, be, w, bias = c["lin0"]
                 with _probe("gen", f_lin0):
                     _lib.check(lib.mrg_gen_linear(0, B, a, rs, ga, be, E, None, None, None, eps, _ptr(y), E, w, bias,
@@ -255,7 +290,7 @@ class GenPlan:
         """The frame loop in one persistent launch (mrg_gen_loop; pointer table order in include/mrg.h)."""
         ptrs = []
         for bi, blk in enumerate(self.blocks):
-            lstm, ffn = blk["lstm"], blk["ffn"]
+            lstm, ffn = blk["mix"], blk["ffn"]
             ptrs += [lstm.w_ih, lstm.b_ih, lstm.b_hh, lstm.ln1_w, lstm.ln1_b, lstm.ff_w, lstm.ff_b, lstm.ln2_w,
                      lstm.ln2_b]
             for ip in blk["integ"]:

@@ -19,7 +19,7 @@ from typing import Any, List, NamedTuple, Optional, Tuple
 from torch import nn
 
 from .layers import LSTM, LSTMBlock as _LSTMBlockModule, LSTMLayerd, LSTMModule, ResidualConnection
-from .mixers import LSTMMixerBlock, LSTMMixerLayerd
+from .mixers import GRUMixerBlock, GRUMixerLayerd, LSTMMixerBlock, LSTMMixerLayerd
 
 
 # ------------------------------------------------------------------ named parameter groups
@@ -35,6 +35,21 @@ class LstmLn(NamedTuple):
 
 class LstmBlock(NamedTuple):
     """u = LN1(LSTM(x) + x), LN2(u ff_w^T + ff_b + u): an LSTM mixer block of the encoder stack."""
+    w_ih: Any
+    w_hh: Any
+    b_ih: Any
+    b_hh: Any
+    ln1_w: Any
+    ln1_b: Any
+    ff_w: Any
+    ff_b: Any
+    ln2_w: Any
+    ln2_b: Any
+
+
+class GruBlock(NamedTuple):
+    """u = LN1(GRU(x) + x), LN2(u ff_w^T + ff_b + u): a GRU mixer block of the generation plan (w_ih /
+    w_hh [3H, H], b_ih / b_hh [3H], torch.nn.GRU's gate order r, z, n)."""
     w_ih: Any
     w_hh: Any
     b_ih: Any
@@ -190,6 +205,69 @@ def embedding_stack_form(metaformer_block) -> Optional[Tuple[List[List[LstmBlock
             layers.append(got[0])
             eps.update(got[1:])
         out.append(layers)
+    if len(eps) != 1:
+        return None
+    return out, eps.pop()
+
+
+def residual_gru(mixer_block):
+    """(GRU, LayerNorm) of a GRUMixerBlock whose mixer is LN(GRU(x) + x) over one unidirectional layer,
+    or None."""
+    if not isinstance(mixer_block, GRUMixerBlock):
+        return None
+    res = mixer_block.mixer
+    if not isinstance(res, ResidualConnection):
+        return None
+    ln, gru = res.layer_norm, res.module.mixer
+    if ln is None or not one_layer_unidirectional(gru):
+        return None
+    return gru, ln
+
+
+def gru_block_form(mixer_block) -> Optional[Tuple[GruBlock, float, float]]:
+    """(GruBlock, eps1, eps2) of a residual_gru block that keeps its width (H -> H) and whose FeedForward
+    is one Linear with a residual LayerNorm, or None."""
+    got = residual_gru(mixer_block)
+    tail = _linear_residual_ln(mixer_block.feed_forward) if got is not None else None
+    if tail is None:
+        return None
+    gru, ln1 = got
+    w_ih, w_hh, b_ih, b_hh = gru.direction_params(0)
+    if w_ih.shape[1] != w_hh.shape[1]:
+        return None
+    lin, ln2 = tail
+    return GruBlock(w_ih, w_hh, b_ih, b_hh, ln1.weight, ln1.bias, lin.weight, lin.bias, ln2.weight,
+                    ln2.bias), ln1.eps, ln2.eps
+
+
+def gru_chain(layerd) -> Optional[list]:
+    """The mixer blocks of a GRUMixerLayerd without input / output projection, or None."""
+    if not (isinstance(layerd, GRUMixerLayerd) and layerd.input_projection is None
+            and layerd.output_projection is None):
+        return None
+    return list(layerd.mixer)
+
+
+def embedding_mixer_form(metaformer_block) -> Optional[Tuple[List[Tuple[str, list]], float]]:
+    """Per modality ("lstm", [LstmBlock]) or ("gru", [GruBlock]) of the block's embedding stacks and
+    their one LayerNorm eps, or None when a stack is neither chain or a block is outside its form.
+    What the generation plan takes (generate.py); the training schedules keep embedding_stack_form."""
+    out, eps = [], set()
+    for layerd in metaformer_block.embedding.modal_embeddings:
+        for kind, chain, block_form in (("lstm", lstm_chain(layerd), lstm_block_form),
+                                        ("gru", gru_chain(layerd), gru_block_form)):
+            if chain is not None:
+                break
+        else:
+            return None
+        layers = []
+        for mb in chain:
+            got = block_form(mb)
+            if got is None:
+                return None
+            layers.append(got[0])
+            eps.update(got[1:])
+        out.append((kind, layers))
     if len(eps) != 1:
         return None
     return out, eps.pop()

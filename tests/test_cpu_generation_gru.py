@@ -1,0 +1,210 @@
+"""Fused generation for GRU embedding mixers, on the CPU: the float64 restatement of mrg_gen_gru
+(tests/gen_gru_ref.py) is torch.nn.GRU's zero-state step, the GRU recognisers of model/forms.py accept
+the config_gru.yaml model and decline each one-edit mutation, the training predicates keep their answers
+for a GRU model, and the entry point is declared, bound and exported.  Models are built, no kernel runs."""
+import copy
+import os
+import re
+
+import pytest
+import torch
+from torch import nn
+
+from multimodalreactiongeneration_amd import configs as C
+from multimodalreactiongeneration_amd.model import Metaformer, forms
+from tests.gen_gru_ref import gen_gru_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E = 256
+SMALL = dict(hidden=32, num_block=2, encoder_num_layer=2, bottleneck=16)
+
+
+# ------------------------------------------------------------------ the restatement is nn.GRU's step
+@pytest.fixture(scope="module")
+def gru_case():
+    torch.manual_seed(11)
+    gru = nn.GRU(E, E, batch_first=True).double()
+    B = 5
+    a, r = torch.randn(B, E, dtype=torch.float64), torch.randn(B, E, dtype=torch.float64)
+    ga, be = torch.randn(E, dtype=torch.float64), torch.randn(E, dtype=torch.float64)
+    ms = torch.randn(B, 6, dtype=torch.float64)
+    fe_w, fe_b = torch.randn(E, 6, dtype=torch.float64), torch.randn(E, dtype=torch.float64)
+    return gru, dict(a=a, r=r, ga=ga, be=be), dict(ms=ms, fe_w=fe_w, fe_b=fe_b)
+
+
+def _through_module(gru, x):
+    with torch.no_grad():
+        y, _ = gru(x.unsqueeze(1), torch.zeros(1, x.shape[0], E, dtype=torch.float64))
+    return y[:, 0]
+
+
+@pytest.mark.parametrize("prologue", ["layernorm", "embedding"])
+def test_restatement_is_the_zero_state_step_of_nn_gru(gru_case, prologue):
+    gru, ln, emb = gru_case
+    kw = ln if prologue == "layernorm" else emb
+    x, h = gen_gru_ref(gru.weight_ih_l0.detach(), gru.bias_ih_l0.detach(), gru.bias_hh_l0.detach(), **kw)
+    if prologue == "layernorm":
+        want_x = torch.nn.functional.layer_norm(ln["a"] + ln["r"], (E,), ln["ga"], ln["be"], 1e-5)
+    else:
+        want_x = emb["ms"] @ emb["fe_w"].t() + emb["fe_b"]
+    assert torch.allclose(x, want_x, rtol=0, atol=1e-12)
+    assert torch.allclose(h, _through_module(gru, x), rtol=0, atol=1e-12)
+
+
+def test_weight_hh_plays_no_part(gru_case):
+    gru, ln, _ = gru_case
+    g2 = copy.deepcopy(gru)
+    x, h = gen_gru_ref(gru.weight_ih_l0.detach(), gru.bias_ih_l0.detach(), gru.bias_hh_l0.detach(), **ln)
+    before = _through_module(g2, x)
+    with torch.no_grad():
+        g2.weight_hh_l0.copy_(torch.randn_like(g2.weight_hh_l0))
+    after = _through_module(g2, x)
+    assert torch.equal(before, after)
+    assert torch.allclose(h, after, rtol=0, atol=1e-12)
+
+
+# ------------------------------------------------------------------ recognisers
+@pytest.fixture(scope="module")
+def small_gru():
+    torch.manual_seed(0)
+    return Metaformer(*C.lstmformer_config(emb_mixers=("gru",) * 3, **SMALL))
+
+
+@pytest.fixture(scope="module")
+def small_lstm():
+    torch.manual_seed(0)
+    return Metaformer(*C.lstmformer_config(**SMALL))
+
+
+def test_field_order():
+    assert forms.GruBlock._fields == forms.LstmBlock._fields
+
+
+@pytest.mark.parametrize("kw", [{}, SMALL])
+def test_gru_config_is_inside_the_gru_forms(kw):
+    m = Metaformer(*C.lstmformer_config(emb_mixers=("gru",) * 3, **kw))
+    for blk in m.metaformer.metaformer_blocks:
+        got = forms.embedding_mixer_form(blk)
+        assert got is not None
+        stacks, eps = got
+        assert eps == 1e-5 and [k for k, _ in stacks] == ["gru"] * len(stacks)
+        for (_, layers), layerd in zip(stacks, blk.embedding.modal_embeddings):
+            chain = forms.gru_chain(layerd)
+            assert chain is not None and len(chain) == len(layers)
+            for form, mb in zip(layers, chain):
+                assert isinstance(form, forms.GruBlock)
+                gru, ln1 = forms.residual_gru(mb)
+                block, eps1, eps2 = forms.gru_block_form(mb)
+                lin, ln2 = mb.feed_forward.feed_forward.module[0], mb.feed_forward.feed_forward.layer_norm
+                want = (gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0, ln1.weight, ln1.bias,
+                        lin.weight, lin.bias, ln2.weight, ln2.bias)
+                assert all(g is w for g, w in zip(block, want)) and all(g is w for g, w in zip(form, want))
+                assert ln1 is mb.mixer.layer_norm and (eps1, eps2) == (ln1.eps, ln2.eps)
+                assert tuple(gru.weight_ih_l0.shape) == (3 * m.metaformer.hidden_dim, m.metaformer.hidden_dim)
+    first = forms.embedding_mixer_form(m.metaformer.metaformer_blocks[0])[0]
+    assert [len(layers) for _, layers in first] == [1, kw.get("encoder_num_layer", 5), kw.get("encoder_num_layer", 5)]
+
+
+def test_mixed_config_names_each_modality(small_lstm):
+    # emb_mixers is indexed by modality (audio, partner motion, self motion); the stacks come main first
+    m = Metaformer(*C.lstmformer_config(emb_mixers=("gru", "lstm", "lstm"), **SMALL))
+    stacks, _ = forms.embedding_mixer_form(m.metaformer.metaformer_blocks[0])
+    assert [k for k, _ in stacks] == ["lstm", "gru", "lstm"]
+    assert [type(l[0]) for _, l in stacks] == [forms.LstmBlock, forms.GruBlock, forms.LstmBlock]
+    later, _ = forms.embedding_mixer_form(m.metaformer.metaformer_blocks[1])
+    assert [k for k, _ in later] == ["lstm"]
+    stacks, eps = forms.embedding_mixer_form(small_lstm.metaformer.metaformer_blocks[0])
+    want, want_eps = forms.embedding_stack_form(small_lstm.metaformer.metaformer_blocks[0])
+    assert eps == want_eps and [k for k, _ in stacks] == ["lstm"] * 3
+    assert all(a is b for (_, ls), ws in zip(stacks, want) for l, w in zip(ls, ws) for a, b in zip(l, w))
+
+
+def _enc(m, i=1, l=1):
+    return m.metaformer.metaformer_blocks[0].embedding.modal_embeddings[i].mixer[l]
+
+
+def _set(obj, name, value):
+    setattr(obj, name, value)
+
+
+def _wider_input(gru):
+    gru.weight_ih_l0 = nn.Parameter(torch.zeros(3 * gru.hidden_size, gru.hidden_size + 4))
+
+
+def results(m):
+    mb = _enc(m)
+    return {"res": forms.residual_gru(mb), "blk": forms.gru_block_form(mb),
+            "emb": forms.embedding_mixer_form(m.metaformer.metaformer_blocks[0]),
+            "emb1": forms.embedding_mixer_form(m.metaformer.metaformer_blocks[1])}
+
+
+def accepted(res):
+    return {k for k, v in res.items() if v is not None}
+
+
+# (what is edited, the keys of results() that must turn to None; every other key must stay)
+LIGHT, FULL = {"res", "blk", "emb"}, {"blk", "emb"}
+MUTATIONS = {
+    "two_layers": (lambda m: _set(_enc(m).mixer.module.mixer, "num_layers", 2), LIGHT),
+    "bidirectional": (lambda m: _set(_enc(m).mixer.module.mixer, "bidirectional", True), LIGHT),
+    "residual_without_ln": (lambda m: _set(_enc(m).mixer, "layer_norm", None), LIGHT),
+    "without_residual": (lambda m: _set(_enc(m), "mixer", _enc(m).mixer.module), LIGHT),
+    "ff_bias_none": (lambda m: _set(_enc(m).feed_forward.feed_forward.module[0], "bias", None), FULL),
+    "ff_without_ln": (lambda m: _set(_enc(m).feed_forward.feed_forward, "layer_norm", None), FULL),
+    "changes_width": (lambda m: _wider_input(_enc(m).mixer.module.mixer), FULL),
+    "ln1_eps": (lambda m: _set(_enc(m).mixer.layer_norm, "eps", 1e-3), {"emb"}),
+    "layerd_input_projection": (lambda m: _set(m.metaformer.metaformer_blocks[0].embedding.modal_embeddings[1],
+                                               "input_projection", nn.Linear(32, 32)), {"emb"}),
+}
+
+
+@pytest.mark.parametrize("name", list(MUTATIONS))
+def test_one_edit_declines_exactly_its_form(small_gru, name):
+    edit, declined = MUTATIONS[name]
+    before = accepted(results(small_gru))
+    m = copy.deepcopy(small_gru)
+    edit(m)
+    res = results(m)
+    assert before == set(res) and accepted(res) == before - declined
+
+
+def test_each_recogniser_declines_the_other_mixer(small_gru, small_lstm):
+    g, l = _enc(small_gru), _enc(small_lstm)
+    assert forms.residual_gru(l) is None and forms.gru_block_form(l) is None
+    assert forms.residual_lstm(g) is None and forms.residual_lstm_form(g) is None and forms.lstm_block_form(g) is None
+    lg = small_gru.metaformer.metaformer_blocks[0].embedding.modal_embeddings[1]
+    ll = small_lstm.metaformer.metaformer_blocks[0].embedding.modal_embeddings[1]
+    assert forms.gru_chain(ll) is None and forms.lstm_chain(lg) is None
+    assert forms.gru_chain(lg) is not None and forms.lstm_chain(ll) is not None
+
+
+@pytest.mark.parametrize("mixers", [("gru",) * 3, ("gru", "lstm", "lstm"), ("lstm", "lstm", "gru")])
+def test_training_predicates_keep_their_answers(mixers):
+    """The encoder stack and the batched first embedding take LSTM embeddings alone."""
+    mf = Metaformer(*C.lstmformer_config(emb_mixers=mixers, **SMALL)).metaformer
+    assert mf._fast_eligible() is False and mf._module_path_only() is False
+    assert forms.embedding_stack_form(mf.metaformer_blocks[0]) is None
+    assert mf._stack_layers(mf.metaformer_blocks[0]) is None
+    if mixers == ("gru",) * 3:
+        assert all(forms.embedding_stack_form(blk) is None for blk in mf.metaformer_blocks)
+        assert all(forms.lstm_chain(lay) is None for blk in mf.metaformer_blocks
+                   for lay in blk.embedding.modal_embeddings)
+
+
+def test_an_mlp_embedding_is_outside():
+    m = Metaformer(*C.lstmformer_config(emb_mixers=("mlp", "gru", "gru"), **SMALL))
+    assert forms.embedding_mixer_form(m.metaformer.metaformer_blocks[0]) is None
+    assert forms.embedding_mixer_form(m.metaformer.metaformer_blocks[1]) is not None   # main chain alone: gru
+
+
+# ------------------------------------------------------------------ the entry point
+def test_entry_point_is_declared_bound_and_exported():
+    from multimodalreactiongeneration_amd import _lib
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mrg.h")).read(), flags=re.S)
+    assert re.search(r"\bint\s+mrg_gen_gru\s*\(", header)
+    assert "mrg_gen_gru" in _lib.SIGNATURES
+    assert _lib.SIGNATURES["mrg_gen_gru"] == _lib.SIGNATURES["mrg_gen_lstm"]   # W_hh is no argument of either
+    if os.path.exists(_lib.LIB_PATH):
+        lib = _lib.load()
+        assert hasattr(lib, "mrg_gen_gru")
+        assert lib.mrg_version() >= 105
