@@ -99,42 +99,35 @@ struct GenFfnArgs {
 };
 
 
-// acc[16 rows x 16 cols] += X[16][k0:k0+NK] W[n][k0:k0+NK]^T on v_mfma_f32_16x16x4_f32: lane l
-// supplies row / column l & 15 at k = kb + 4 (l >> 4) + j for the j-th product of a 16-k group, so
-// its four operands of a group are one float4 (A and B use the same k of each product pair).
-// gen_wload issues the lane's weight loads (at kernel start: independent of the prologue)
-template <int NK>
-__device__ __forceinline__ void gen_wload(const float* __restrict__ wrow, int k0, int lane, float4 (&w)[NK / 16]) {
-#pragma unroll
-  for (int i = 0; i < NK / 16; ++i) w[i] = *reinterpret_cast<const float4*>(wrow + k0 + 16 * i + 4 * (lane >> 4));
-}
-template <int KP, int NK>
-__device__ __forceinline__ gv4 gen_mfma(const float* xs, const float4 (&w)[NK / 16], int k0, int lane, gv4 acc) {
-  const int m = lane & 15, q = lane >> 4;
-#pragma unroll
-  for (int i = 0; i < NK / 16; ++i) {
-    const float4 x = *reinterpret_cast<const float4*>(xs + m * KP + k0 + 16 * i + 4 * q);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.x, w[i].x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.y, w[i].y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.z, w[i].z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.w, w[i].w, acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// the four waves' k-quarter partial tiles into red[4][16][17]; accumulator register i of lane l is
-// row 4 (l >> 4) + i, column l & 15
-__device__ __forceinline__ void gen_park(float (*red)[GR][17], int wave, int lane, gv4 acc) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) red[wave][4 * (lane >> 4) + i][lane & 15] = acc[i];
-}
-__device__ __forceinline__ float gen_sum(const float (*red)[GR][17], int m, int n) {
-  return (red[0][m][n] + red[1][m][n]) + (red[2][m][n] + red[3][m][n]);
-}
-
 // Every launch below first issues the loads that do not depend on the previous launch (this lane's
-// weight operands, the LayerNorm gamma / beta, the biases of its outputs), then the activation rows
-// (clamped past B, zeroed after), so a kernel waits about one memory round trip before its products.
+// weight fragments, gl_wload; the LayerNorm gamma / beta; the biases of its outputs), then all of its
+// activation rows (gen_rows_ld: clamped past B; zeroed after, gen_row_put) before the first LayerNorm
+// reduction, so a kernel waits about one memory round trip before its products (gl_mma, gen_loop.h).
+
+// Rows wave + 4 i (i < 4) of this workgroup's 16 of N [B][ld] inputs, the lane's four columns, into
+// x[input][i]; rows past B read row B - 1 (in bounds, no branch around a load)
+template <int N>
+__device__ __forceinline__ void gen_rows_ld(const float* const* src, long ld, int row0, int B, int wave, int lane,
+                                            float4 (*x)[GR / 4]) {
+#pragma unroll
+  for (int i = 0; i < GR / 4; ++i) {
+    const long at = (long)min(row0 + wave + 4 * i, B - 1) * ld + 4 * lane;
+#pragma unroll
+    for (int j = 0; j < N; ++j) x[j][i] = gen_ld4(src[j] + at);
+  }
+}
+// Is column k in this workgroup's share of the 256-wide rows that `tiles` column tiles write back between them?
+__device__ __forceinline__ bool gen_my_share(int k, int tiles) {
+  const int share = GE / tiles, sh0 = (blockIdx.x % tiles) * share;
+  return k >= sh0 && k < sh0 + share;
+}
+// Four columns of batch row b: zero past B, else to xw[at] when they are this workgroup's to keep (xw
+// null: not kept); to LDS
+__device__ __forceinline__ void gen_row_put(float4 v, int b, int B, float* xw, long at, float* xs) {
+  if (xw && b < B) *reinterpret_cast<float4*>(xw + at) = v;
+  if (b >= B) v = gen_zero4();
+  *reinterpret_cast<float4*>(xs) = v;
+}
 
 // The recurrent mixers' input rows X [16][GE] of this workgroup into xs (rows past B zero), and its
 // share (GE / gridDim.x columns) of them into p.xw.  PRO 0: X = ms W_fe^T + b_fe; PRO 1: X = LN(a + r)
@@ -142,7 +135,6 @@ template <int PRO>
 __device__ __forceinline__ void gen_mixer_x(const GenLstmArgs& p, float (*xs)[GE + 4], float (*msl)[16]) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row0 = blockIdx.y * GR;
-  const int share = GE / gridDim.x;   // X columns this workgroup writes back
   if (PRO == 0) {
     // X = ms W_fe^T + b_fe (K = fm <= 16): the 16 rows' inputs staged in LDS, thread = column
     const int k = tid;
@@ -155,7 +147,7 @@ __device__ __forceinline__ void gen_mixer_x(const GenLstmArgs& p, float (*xs)[GE
       msl[m][f] = (f < p.fm && row0 + m < p.B) ? p.ms[(long)(row0 + m) * p.fm + f] : 0.0f;
     }
     __syncthreads();
-    const bool mine = k >= blockIdx.x * share && k < (blockIdx.x + 1) * share;
+    const bool mine = gen_my_share(k, gridDim.x);
 #pragma unroll
     for (int m = 0; m < GR; ++m) {
       float s = 0.0f;
@@ -166,23 +158,16 @@ __device__ __forceinline__ void gen_mixer_x(const GenLstmArgs& p, float (*xs)[GE
       xs[m][k] = v;
     }
   } else {
-    const float4 gg = gen_ld4(p.ga + 4 * lane), bb = gen_ld4(p.be + 4 * lane);
-    float4 va[GR / 4], vr[GR / 4];
-#pragma unroll
-    for (int i = 0; i < GR / 4; ++i) {
-      const long b = min(row0 + wave + 4 * i, p.B - 1);
-      va[i] = gen_ld4(p.a + b * GE + 4 * lane);
-      vr[i] = gen_ld4(p.r + b * GE + 4 * lane);
-    }
+    const GlLn ln = gl_lnp(p.ga, p.be, lane);
+    const float* src[2] = {p.a, p.r};
+    float4 x[2][GR / 4];
+    gen_rows_ld<2>(src, GE, row0, p.B, wave, lane, x);
     const int k = 4 * lane;
-    const bool mine = k >= blockIdx.x * share && k < (blockIdx.x + 1) * share;
+    float* keep = gen_my_share(k, gridDim.x) ? p.xw : nullptr;
 #pragma unroll
     for (int i = 0; i < GR / 4; ++i) {
       const int m = wave + 4 * i, b = row0 + m;
-      float4 v = gen_ln(gen_add4(va[i], vr[i]), gg, bb, p.eps);
-      if (b >= p.B) v = gen_zero4();
-      else if (mine) *reinterpret_cast<float4*>(p.xw + (long)b * GE + k) = v;
-      *reinterpret_cast<float4*>(&xs[m][k]) = v;
+      gen_row_put(gen_ln(gen_add4(x[0][i], x[1][i]), ln.g, ln.b, p.eps), b, p.B, keep, (long)b * GE + k, &xs[m][k]);
     }
   }
 }
@@ -193,13 +178,13 @@ template <int PRO>
 __global__ __launch_bounds__(256) void gen_lstm_kernel(GenLstmArgs p) {
   constexpr int KP = GE + 4;
   __shared__ __attribute__((aligned(16))) float xs[GR][KP];
-  __shared__ float red[4][GR][17];
+  __shared__ float red[4][1][GR][17];
   __shared__ float msl[GR][16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row0 = blockIdx.y * GR, u0 = 4 * blockIdx.x;
   const int n = lane & 15;
-  float4 w[GE / 4 / 16];
-  gen_wload<GE / 4>(p.w_ih + (long)((n >> 2) * GE + u0 + (n & 3)) * GE, wave * (GE / 4), lane, w);
+  GlW<GE> w;
+  gl_wload<GE>(w, p.w_ih + (long)((n >> 2) * GE + u0 + (n & 3)) * GE, wave, lane);
   // cell thread (m, j): its unit's biases
   const int cm = tid >> 2, cj = tid & 3, cu = u0 + cj;
   float bi = 0.f, bg = 0.f, bo = 0.f;
@@ -210,14 +195,12 @@ __global__ __launch_bounds__(256) void gen_lstm_kernel(GenLstmArgs p) {
   }
   gen_mixer_x<PRO>(p, xs, msl);
   __syncthreads();
-  gv4 acc = gv4{0.f, 0.f, 0.f, 0.f};
-  acc = gen_mfma<KP, GE / 4>(&xs[0][0], w, wave * (GE / 4), lane, acc);
-  gen_park(red, wave, lane, acc);
+  gl_park(red, 0, wave, lane, gl_mma<GE>(&xs[0][0], KP, w, lane, wave));
   __syncthreads();
   if (tid < 4 * GR && row0 + cm < p.B) {
-    const float zi = gen_sum(red, cm, cj) + bi;
-    const float zg = gen_sum(red, cm, 8 + cj) + bg;
-    const float zo = gen_sum(red, cm, 12 + cj) + bo;
+    const float zi = gl_sum(red, 0, cm, cj) + bi;
+    const float zg = gl_sum(red, 0, cm, 8 + cj) + bg;
+    const float zo = gl_sum(red, 0, cm, 12 + cj) + bo;
     const float c = sigmoidf_(zi) * tanhf_(zg);   // f c0 + i g with c0 = 0
     p.h[(long)(row0 + cm) * GE + cu] = sigmoidf_(zo) * tanhf_(c);
   }
@@ -232,14 +215,13 @@ template <int PRO>
 __global__ __launch_bounds__(256) void gen_gru_kernel(GenLstmArgs p) {
   constexpr int KP = GE + 4;
   __shared__ __attribute__((aligned(16))) float xs[GR][KP];
-  __shared__ float red[3][4][GR][17];
+  __shared__ float red[4][3][GR][17];
   __shared__ float msl[GR][16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row0 = blockIdx.y * GR, u0 = 16 * blockIdx.x;
-  float4 w[3][GE / 4 / 16];
+  GlW<GE> w[3];
 #pragma unroll
-  for (int g = 0; g < 3; ++g)
-    gen_wload<GE / 4>(p.w_ih + (long)(g * GE + u0 + (lane & 15)) * GE, wave * (GE / 4), lane, w[g]);
+  for (int g = 0; g < 3; ++g) gl_wload<GE>(w[g], p.w_ih + (long)(g * GE + u0 + (lane & 15)) * GE, wave, lane);
   // cell thread (m, j): its unit's biases
   const int cm = tid >> 4, cj = tid & 15, cu = u0 + cj;
   const float bir = p.b_ih[cu], biz = p.b_ih[GE + cu], bin = p.b_ih[2 * GE + cu];
@@ -247,16 +229,12 @@ __global__ __launch_bounds__(256) void gen_gru_kernel(GenLstmArgs p) {
   gen_mixer_x<PRO>(p, xs, msl);
   __syncthreads();
 #pragma unroll
-  for (int g = 0; g < 3; ++g) {
-    gv4 acc = gv4{0.f, 0.f, 0.f, 0.f};
-    acc = gen_mfma<KP, GE / 4>(&xs[0][0], w[g], wave * (GE / 4), lane, acc);
-    gen_park(red[g], wave, lane, acc);
-  }
+  for (int g = 0; g < 3; ++g) gl_park(red, g, wave, lane, gl_mma<GE>(&xs[0][0], KP, w[g], lane, wave));
   __syncthreads();
   if (row0 + cm < p.B) {
-    const float rg = sigmoidf_((gen_sum(red[0], cm, cj) + bir) + bhr);
-    const float zg = sigmoidf_((gen_sum(red[1], cm, cj) + biz) + bhz);
-    const float ng = tanhf_((gen_sum(red[2], cm, cj) + bin) + rg * bhn);
+    const float rg = sigmoidf_((gl_sum(red, 0, cm, cj) + bir) + bhr);
+    const float zg = sigmoidf_((gl_sum(red, 1, cm, cj) + biz) + bhz);
+    const float ng = tanhf_((gl_sum(red, 2, cm, cj) + bin) + rg * bhn);
     p.h[(long)(row0 + cm) * GE + cu] = (1.0f - zg) * ng;   // + z h_0 with h_0 = 0
   }
 }
@@ -271,61 +249,43 @@ __global__ __launch_bounds__(256) void gen_linear_kernel(GenLinArgs p) {
   constexpr int KP = K + 4;
   constexpr int NH = PRO == 2 ? 2 : 1;
   __shared__ __attribute__((aligned(16))) float xs[GR][KP];
-  __shared__ float red[4][GR][17];
+  __shared__ float red[4][1][GR][17];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row0 = blockIdx.y * GR;
   const int n0 = 16 * blockIdx.x;
   const int half = PRO == 1 ? n0 / GE : 0;           // PRO 1: integrator of this column tile
-  const int tiles = PRO == 1 ? gridDim.x / 2 : gridDim.x;
-  const int share = GE / tiles, sh0 = (blockIdx.x % tiles) * share;
   const int nl = n0 - half * GE;                     // first row of this half's weight
-  float4 w[K / 4 / 16];
-  gen_wload<K / 4>(p.w[half] + (long)(nl + (lane & 15)) * K, wave * (K / 4), lane, w);
+  GlW<K> w;
+  gl_wload<K>(w, p.w[half] + (long)(nl + (lane & 15)) * K, wave, lane);
   const float bias = p.bias[half][nl + (tid & 15)];
   const int k = 4 * lane;
-  float4 gg[NH], bb[NH], g2 = gen_zero4(), b2 = gen_zero4();
+  GlLn ln[NH], ln2 = GlLn{gen_zero4(), gen_zero4()};
 #pragma unroll
-  for (int hh = 0; hh < NH; ++hh) {
-    gg[hh] = gen_ld4(p.ga[hh] + k);
-    bb[hh] = gen_ld4(p.be[hh] + k);
-  }
-  if (PRO == 1) {
-    g2 = gen_ld4(p.ga2[half] + k);
-    b2 = gen_ld4(p.be2[half] + k);
-  }
+  for (int hh = 0; hh < NH; ++hh) ln[hh] = gl_lnp(p.ga[hh], p.be[hh], lane);
+  if (PRO == 1) ln2 = gl_lnp(p.ga2[half], p.be2[half], lane);
   {
-    float4 va[GR / 4][NH], vr[GR / 4][NH], v2[GR / 4];
-#pragma unroll
-    for (int i = 0; i < GR / 4; ++i) {
-      const long b = min(row0 + wave + 4 * i, p.B - 1);
-#pragma unroll
-      for (int hh = 0; hh < NH; ++hh) {
-        va[i][hh] = gen_ld4(p.a[hh] + b * p.lda + k);
-        vr[i][hh] = gen_ld4(p.r[hh] + b * p.lda + k);
-      }
-      if (PRO == 1) v2[i] = gen_ld4(p.a2[half] + b * p.lda + k);
-    }
-    const bool mine = p.xw && k >= sh0 && k < sh0 + share;
+    // x[2 hh], x[2 hh + 1]: the first LayerNorm's inputs of half hh; PRO 1: x[2] the second's
+    constexpr int NX = PRO == 0 ? 2 : PRO == 1 ? 3 : 4;
+    const float* src[4] = {p.a[0], p.r[0], PRO == 1 ? p.a2[half] : p.a[1], p.r[1]};
+    float4 x[NX][GR / 4];
+    gen_rows_ld<NX>(src, p.lda, row0, p.B, wave, lane, x);
+    float* keep = gen_my_share(k, PRO == 1 ? gridDim.x / 2 : gridDim.x) ? p.xw : nullptr;
 #pragma unroll
     for (int i = 0; i < GR / 4; ++i) {
       const int m = wave + 4 * i, b = row0 + m;
 #pragma unroll
       for (int hh = 0; hh < NH; ++hh) {
-        float4 v = gen_ln(gen_add4(va[i][hh], vr[i][hh]), gg[hh], bb[hh], p.eps);
-        if (PRO == 1) v = gen_ln(gen_add4(v2[i], v), g2, b2, p.eps);
-        if (b >= p.B) v = gen_zero4();
-        else if (mine) *reinterpret_cast<float4*>(p.xw + b * p.ldxw + half * GE + k) = v;
-        *reinterpret_cast<float4*>(&xs[m][hh * GE + k]) = v;
+        float4 v = gen_ln(gen_add4(x[2 * hh][i], x[2 * hh + 1][i]), ln[hh].g, ln[hh].b, p.eps);
+        if (PRO == 1) v = gen_ln(gen_add4(x[2][i], v), ln2.g, ln2.b, p.eps);
+        gen_row_put(v, b, p.B, keep, b * p.ldxw + half * GE + k, &xs[m][hh * GE + k]);
       }
     }
   }
   __syncthreads();
-  gv4 acc = gv4{0.f, 0.f, 0.f, 0.f};
-  acc = gen_mfma<KP, K / 4>(&xs[0][0], w, wave * (K / 4), lane, acc);
-  gen_park(red, wave, lane, acc);
+  gl_park(red, 0, wave, lane, gl_mma<K>(&xs[0][0], KP, w, lane, wave));
   __syncthreads();
   const int m = tid >> 4, nn = tid & 15, b = row0 + m;
-  if (b < p.B) p.out[b * p.ldo + n0 + nn] = gen_sum(red, m, nn) + bias;
+  if (b < p.B) p.out[b * p.ldo + n0 + nn] = gl_sum(red, 0, m, nn) + bias;
 }
 
 // ------------------------------------------------------------------ FeedForward (Linear-ReLU-Linear)
@@ -337,65 +297,48 @@ __global__ __launch_bounds__(256) void gen_ffn_kernel(GenFfnArgs p) {
   constexpr int KP = GE + 4, HP = GHB + 4;
   __shared__ __attribute__((aligned(16))) float xs[GR][KP];
   __shared__ __attribute__((aligned(16))) float hs[GR][HP];
-  __shared__ float red[4][GR][17];
+  __shared__ float red[4][1][GR][17];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row0 = blockIdx.y * GR;
   const int n0 = 16 * blockIdx.x;
   const int hc = 16 * wave + (lane & 15);            // this lane's hidden column
-  float4 w1[GE / 16];
-  gen_wload<GE>(p.w1 + (long)hc * GE, 0, lane, w1);
+  GlW<4 * GE> w1;                                    // the whole E-wide k range of the wave's own tile
+  gl_wload<4 * GE>(w1, p.w1 + (long)hc * GE, 0, lane);
   const float b1 = p.b1[hc];
   const int nw = n0 + (lane & 15);
   const bool nok = nw < p.N;
-  // a column past N (the output FeedForward's 6 outputs) multiplies a zero row
-  float4 w2 = *reinterpret_cast<const float4*>(p.w2 + (long)(nok ? nw : 0) * GHB + 16 * wave + 4 * (lane >> 4));
-  if (!nok) w2 = gen_zero4();
+  // a column past N (the output FeedForward's 6 outputs) multiplies zeroed fragments of a valid weight row
+  GlW<GHB> w2;
+  gl_wload<GHB>(w2, p.w2 + (long)(nok ? nw : 0) * GHB, wave, lane);
+  if (!nok) w2.v[0] = gen_zero4();
   const int ocol = n0 + (tid & 15);
   const float b2 = ocol < p.N ? p.b2[ocol] : 0.0f;
   {
-    float4 gg = gen_zero4(), bb = gen_zero4();
-    if (PRO == 1) {
-      gg = gen_ld4(p.ga + 4 * lane);
-      bb = gen_ld4(p.be + 4 * lane);
-    }
-    float4 va[GR / 4], vr[GR / 4];
-#pragma unroll
-    for (int i = 0; i < GR / 4; ++i) {
-      const long b = min(row0 + wave + 4 * i, p.B - 1);
-      va[i] = gen_ld4(p.a + b * GE + 4 * lane);
-      if (PRO == 1) vr[i] = gen_ld4(p.r + b * GE + 4 * lane);
-    }
+    GlLn ln = GlLn{gen_zero4(), gen_zero4()};
+    if (PRO == 1) ln = gl_lnp(p.ga, p.be, lane);
+    const float* src[2] = {p.a, p.r};
+    float4 x[1 + PRO][GR / 4];
+    gen_rows_ld<1 + PRO>(src, GE, row0, p.B, wave, lane, x);
 #pragma unroll
     for (int i = 0; i < GR / 4; ++i) {
       const int m = wave + 4 * i;
-      float4 v = va[i];
-      if (PRO == 1) v = gen_ln(gen_add4(v, vr[i]), gg, bb, p.eps);
-      if (row0 + m >= p.B) v = gen_zero4();
-      *reinterpret_cast<float4*>(&xs[m][4 * lane]) = v;
+      float4 v = x[0][i];
+      if (PRO == 1) v = gen_ln(gen_add4(v, x[PRO][i]), ln.g, ln.b, p.eps);
+      gen_row_put(v, row0 + m, p.B, nullptr, 0, &xs[m][4 * lane]);
     }
   }
   __syncthreads();
   {
-    gv4 acc = gv4{0.f, 0.f, 0.f, 0.f};
-    acc = gen_mfma<KP, GE>(&xs[0][0], w1, 0, lane, acc);
+    const gv4 acc = gl_mma<4 * GE>(&xs[0][0], KP, w1, lane, 0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) hs[4 * (lane >> 4) + i][hc] = fmaxf(acc[i] + b1, 0.0f);
   }
   __syncthreads();
-  gv4 acc = gv4{0.f, 0.f, 0.f, 0.f};
-  {
-    const int m = lane & 15, q = lane >> 4, k = 16 * wave;
-    const float4 x = *reinterpret_cast<const float4*>(&hs[m][k + 4 * q]);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.x, w2.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.y, w2.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.z, w2.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.w, w2.w, acc, 0, 0, 0);
-  }
-  gen_park(red, wave, lane, acc);
+  gl_park(red, 0, wave, lane, gl_mma<GHB>(&hs[0][0], HP, w2, lane, wave));
   __syncthreads();
   const int m = tid >> 4, nn = tid & 15, b = row0 + m;
   if (b >= p.B || ocol >= p.N) return;
-  const float y = gen_sum(red, m, nn) + b2;
+  const float y = gl_sum(red, 0, m, nn) + b2;
   if (OUT == 0) {
     p.out[(long)b * p.N + ocol] = y;
   } else {
@@ -768,36 +711,37 @@ using namespace mrg;
 
 static int gen_rows(int B) { return (B + GR - 1) / GR; }
 
-// X [B][256] from the self-motion input (block 0: ms W_fe^T + b_fe, fm <= 16) or from the previous
-// block's FeedForward (LN(a + r)); gates = X W_ih^T + b_ih + b_hh; zero-state cell -> h [B][256].
+// The recurrent mixers' launch: X [B][256] from the self-motion input (block 0: ms W_fe^T + b_fe,
+// fm <= 16) or from the previous block's FeedForward (LN(a + r)) into xw, then the mixer's zero-state step
+// -> h [B][256].  `units`: the units a workgroup's column tiles serve.
+template <typename Kern>
+static int gen_mixer_launch(const char* name, Kern from_ms, Kern from_ln, int units, const GenLstmArgs& p,
+                            hipStream_t stream) {
+  if (p.B == 0) return 0;
+  MRG_REQUIRE(p.B > 0 && p.xw && p.w_ih && p.b_ih && p.b_hh && p.h, "%s: B >= 0 and xw / w_ih / b_ih / b_hh / h (B=%d)",
+              name, p.B);
+  MRG_REQUIRE(!(p.ms && (p.a || p.r || p.ga || p.be)), "%s: give ms or the LayerNorm inputs, not both", name);
+  MRG_REQUIRE(p.ms ? (p.fm >= 1 && p.fm <= 16 && p.fe_w && p.fe_b) : (p.a && p.r && p.ga && p.be),
+              "%s: give ms + feature embedding (fm <= 16) or the LayerNorm inputs (fm=%d)", name, p.fm);
+  klaunch(p.ms ? from_ms : from_ln, dim3(GE / units, gen_rows(p.B)), 256, 0, stream, p);
+  return check_launch(name);
+}
+
+// The LSTM mixer: gates = X W_ih^T + b_ih + b_hh (w_ih [1024][256], gates i, f, g, o), zero-state cell.
 MRG_API int mrg_gen_lstm(int B, int fm, const float* ms, const float* fe_w, const float* fe_b, const float* a,
                          const float* r, const float* ga, const float* be, float eps, float* xw, const float* w_ih,
                          const float* b_ih, const float* b_hh, float* h, hipStream_t stream) {
-  if (B == 0) return 0;
-  MRG_REQUIRE(ms ? (fm >= 1 && fm <= 16 && fe_w && fe_b) : (a && r && ga && be),
-              "mrg_gen_lstm: give ms + feature embedding (fm <= 16) or the LayerNorm inputs");
-  GenLstmArgs p{B, fm, ms, fe_w, fe_b, a, r, ga, be, eps, xw, w_ih, b_ih, b_hh, h};
-  const dim3 grid(GE / 4, gen_rows(B));
-  if (ms) klaunch(gen_lstm_kernel<0>, grid, 256, 0, stream, p);
-  else klaunch(gen_lstm_kernel<1>, grid, 256, 0, stream, p);
-  return check_launch("gen_lstm_kernel");
+  return gen_mixer_launch("mrg_gen_lstm", gen_lstm_kernel<0>, gen_lstm_kernel<1>, 4,
+                          {B, fm, ms, fe_w, fe_b, a, r, ga, be, eps, xw, w_ih, b_ih, b_hh, h}, stream);
 }
 
-// The GRU mixer's form of mrg_gen_lstm: the same two prologues into xw [B][256], then the zero-state
-// torch.nn.GRU step (gates r, z, n; w_ih [768][256], b_ih / b_hh [768]; W_hh is not read) -> h [B][256].
+// The GRU mixer: the zero-state torch.nn.GRU step (gates r, z, n; w_ih [768][256], b_ih / b_hh [768];
+// W_hh is not read).
 MRG_API int mrg_gen_gru(int B, int fm, const float* ms, const float* fe_w, const float* fe_b, const float* a,
                         const float* r, const float* ga, const float* be, float eps, float* xw, const float* w_ih,
                         const float* b_ih, const float* b_hh, float* h, hipStream_t stream) {
-  if (B == 0) return 0;
-  MRG_REQUIRE(B > 0 && xw && w_ih && b_ih && b_hh && h, "mrg_gen_gru: B >= 0 and xw / w_ih / b_ih / b_hh / h (B=%d)", B);
-  MRG_REQUIRE(!(ms && (a || r || ga || be)), "mrg_gen_gru: give ms or the LayerNorm inputs, not both");
-  MRG_REQUIRE(ms ? (fm >= 1 && fm <= 16 && fe_w && fe_b) : (a && r && ga && be),
-              "mrg_gen_gru: give ms + feature embedding (fm <= 16) or the LayerNorm inputs (fm=%d)", fm);
-  GenLstmArgs p{B, fm, ms, fe_w, fe_b, a, r, ga, be, eps, xw, w_ih, b_ih, b_hh, h};
-  const dim3 grid(GE / 16, gen_rows(B));
-  if (ms) klaunch(gen_gru_kernel<0>, grid, 256, 0, stream, p);
-  else klaunch(gen_gru_kernel<1>, grid, 256, 0, stream, p);
-  return check_launch("gen_gru_kernel");
+  return gen_mixer_launch("mrg_gen_gru", gen_gru_kernel<0>, gen_gru_kernel<1>, 16,
+                          {B, fm, ms, fe_w, fe_b, a, r, ga, be, eps, xw, w_ih, b_ih, b_hh, h}, stream);
 }
 
 // mode 0: out [B][256] = LN(a + r) W^T + b, the normalised rows into xw [B][256]

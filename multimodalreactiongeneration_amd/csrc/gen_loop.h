@@ -1,7 +1,8 @@
-// Shared pieces of the persistent frame loops (gen.hip: lstmformer generation; ssd_loop.hip: the
-// scheduled-sampling decode of lstm_with_sampling): 256-wide rows held 4 values per lane, the
-// LayerNorm on them, exact-f32 16 x 16 MFMA tiles of 8 batch rows, and the {tag, value} granule
-// gathers through which the members of a row group hand each stage's output to each other.
+// Shared pieces of the generation kernels (gen.hip: lstmformer generation, per launch and as one
+// persistent frame loop; ssd_loop.hip: the scheduled-sampling decode of lstm_with_sampling): 256-wide
+// rows held 4 values per lane, the LayerNorm on them, exact-f32 16 x 16 MFMA tiles over 16 LDS rows (the
+// loops fill 8 of them), and the {tag, value} granule gathers through which the members of a loop's row
+// group hand each stage's output to each other.
 #pragma once
 #include "lstm_common.h"
 
@@ -111,12 +112,15 @@ __device__ __forceinline__ void gl_ln_row(const float* a, const float* b, const 
   if (out2) *reinterpret_cast<float4*>(out2 + 4 * lane) = v;
 }
 
-// the four waves' partial tiles of tile q into red[.][q]
-__device__ __forceinline__ void gl_park(float (*red)[4][16][17], int q, int wave, int lane, gv4 acc) {
+// the four waves' partial tiles of tile q (of the Q a stage keeps) into red[.][q]; accumulator register i
+// of lane l is row 4 (l >> 4) + i, column l & 15
+template <int Q>
+__device__ __forceinline__ void gl_park(float (*red)[Q][16][17], int q, int wave, int lane, gv4 acc) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) red[wave][q][4 * (lane >> 4) + i][lane & 15] = acc[i];
 }
-__device__ __forceinline__ float gl_sum(const float (*red)[4][16][17], int q, int m, int n) {
+template <int Q>
+__device__ __forceinline__ float gl_sum(const float (*red)[Q][16][17], int q, int m, int n) {
   return (red[0][q][m][n] + red[1][q][m][n]) + (red[2][q][m][n] + red[3][q][m][n]);
 }
 

@@ -1,5 +1,5 @@
 """Fused generation for GRU embedding mixers, on the CPU: the float64 restatement of mrg_gen_gru
-(tests/gen_gru_ref.py) is torch.nn.GRU's zero-state step, the GRU recognisers of model/forms.py accept
+(tests/gen_ref.py) is torch.nn.GRU's zero-state step, the GRU recognisers of model/forms.py accept
 the config_gru.yaml model and decline each one-edit mutation, the training predicates keep their answers
 for a GRU model, and the entry point is declared, bound and exported.  Models are built, no kernel runs."""
 import copy
@@ -12,7 +12,7 @@ from torch import nn
 
 from multimodalreactiongeneration_amd import configs as C
 from multimodalreactiongeneration_amd.model import Metaformer, forms
-from tests.gen_gru_ref import gen_gru_ref
+from tests.gen_ref import gen_gru_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E = 256

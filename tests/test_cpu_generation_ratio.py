@@ -1,13 +1,13 @@
 """CPU-only checks of the ratio > 1 generation plan's new entry point: mrg_gen_attention is declared,
 exported and bound, refuses bad arguments before any launch, and its float64 restatement
-(tests/gen_attention_ref.py) is torch.nn.MultiheadAttention's context at one query over r keys."""
+(tests/gen_ref.py) is torch.nn.MultiheadAttention's context at one query over r keys."""
 import os
 import re
 
 import pytest
 import torch
 
-from tests.gen_attention_ref import gen_attention_ref
+from tests.gen_ref import gen_attention_ref
 from tests.golden_util import rel_err
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

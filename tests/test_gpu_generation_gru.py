@@ -1,49 +1,22 @@
 """Fused generation for GRU embedding mixers (config_gru.yaml): mrg_gen_gru (csrc/gen.hip) through the C
-ABI against the float64 restatement of tests/gen_gru_ref.py, and the GenPlan of generate.py with GRU main
+ABI against the float64 restatement of tests/gen_ref.py, and the GenPlan of generate.py with GRU main
 chains and / or GRU side stacks against the per-frame module forward (lstmformer.py:426-547).
 
 Kernel bar: rel_err < 1e-4 (max |a - ref| / max |ref|, tests.golden_util: the project's kernel-vs-float64
 bar).  Plan bar: rel_err(fast, slow) < 1e-5, the bar of test_generation_ratio_fused_matches_module_path:
 both paths do fp32 arithmetic on the same kernel family."""
-import functools
-
-import numpy as np
 import pytest
 import torch
 
-from tests.gen_gru_ref import gen_gru_ref
+from tests.gen_ref import gen_gru_ref
+from tests.gen_util import (DEV, E, GUARD, _case, _done, _fast_both_ways, _graph_replay_is_eager,  # noqa: F401
+                            _guarded, _inside, _lib, _model, _poisoned, _ptr, _stream)
 from tests.golden_util import rel_err
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
-DEV = "cuda:0"
-E = 256
-GUARD = 512   # NaN floats on either side of xw and h
 EPS = 1e-5
 GRU3 = ("gru",) * 3
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _done():
-    yield
-    from multimodalreactiongeneration_amd import functional as Fn
-    torch.cuda.synchronize()
-    Fn.check_errors()
-
-
-def _lib():
-    from multimodalreactiongeneration_amd import _lib as L
-    return L.load()
-
-
-def _ptr(t, off=0):
-    from multimodalreactiongeneration_amd.functional import _ptr as p
-    return None if t is None else p(t, off)
-
-
-def _stream():
-    from multimodalreactiongeneration_amd.functional import _stream as s
-    return s()
 
 
 def _inputs(B, fm, seed):
@@ -58,25 +31,16 @@ def _inputs(B, fm, seed):
     return d
 
 
-def _poisoned(t):
-    """t on the device, followed by one more NaN-filled row (a read past row B - 1 poisons the result)."""
-    return torch.cat([t, torch.full_like(t[:1], float("nan"))]).to(DEV).contiguous()
-
-
 def _run(B, fm, d):
     """(xw, h) [B, 256] of one call, each between two NaN guard zones that must stay NaN."""
     dd = {k: (_poisoned(v) if k in ("ms", "a", "r") else v.to(DEV).contiguous()) for k, v in d.items()}
-    bufs = [torch.full((2 * GUARD + B * E,), float("nan"), device=DEV) for _ in range(2)]
+    bufs = [_guarded(B * E) for _ in range(2)]
     p = lambda k: _ptr(dd.get(k))
     rc = _lib().mrg_gen_gru(B, fm, p("ms"), p("fe_w"), p("fe_b"), p("a"), p("r"), p("ga"), p("be"), EPS,
                             _ptr(bufs[0], GUARD), p("w_ih"), p("b_ih"), p("b_hh"), _ptr(bufs[1], GUARD), _stream())
     torch.cuda.synchronize()
     assert rc == 0, _lib().mrg_last_error()
-    out = []
-    for buf in bufs:
-        assert bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[GUARD + B * E:]).all())
-        out.append(buf[GUARD:GUARD + B * E].view(B, E).cpu())
-    return out
+    return [_inside(buf, B, E) for buf in bufs]
 
 
 @pytest.mark.parametrize("fm", [0, 3, 6, 16])   # 0: X = LN(a + r); else X = ms W_fe^T + b_fe
@@ -119,12 +83,6 @@ def test_gen_gru_refusals():
 
 
 # ------------------------------------------------------------------ which models get a plan
-def _model(**kw):
-    from multimodalreactiongeneration_amd import configs as C
-    from multimodalreactiongeneration_amd.model import Metaformer
-    return Metaformer(*C.lstmformer_config(**kw)).to(DEV)
-
-
 @pytest.mark.parametrize("mixers,r", [(GRU3, 1), (GRU3, 2), (GRU3, 8), (("gru", "lstm", "lstm"), 2),
                                       (("lstm", "lstm", "gru"), 1), (("lstm", "gru", "lstm"), 1)])
 def test_plan_exists(mixers, r):
@@ -134,7 +92,7 @@ def test_plan_exists(mixers, r):
     plan = plan_for(m.eval())
     assert plan is not None and plan.ratio == r
     # emb_mixers is indexed by modality (audio, partner motion, self motion = the main chain)
-    assert [b["kind"] for b in plan.blocks] == [mixers[2]] * 5
+    assert [b.kind for b in plan.blocks] == [mixers[2]] * 5
     assert [k for k, _ in plan.enc] == list(mixers[:2])
     assert plan.loop_form is (mixers[2] == "lstm")
 
@@ -167,26 +125,10 @@ def test_plan_still_declined():
 # ------------------------------------------------------------------ the plan against the module path
 # (mixers by modality: audio, partner motion, self motion; ratio, B, T).  (2, 64, 9) has T * B = 576
 # audio sequences, more than one launch of the GRU recurrence takes on 256 CUs
-# (generate.GenPlan._encoder_steps), so its chunks are joined.  The last case's main chain is an LSTM:
+# (generate.GenPlan._side_stack), so its chunks are joined.  The last case's main chain is an LSTM:
 # the persistent loop serves it, reading the GRU partner-motion stack's hoisted attention output.
 CASES = [(GRU3, 1, 3, 5), (GRU3, 8, 3, 5), (GRU3, 2, 17, 4), (GRU3, 2, 64, 9), (("gru", "lstm", "lstm"), 2, 3, 5),
          (("lstm", "lstm", "gru"), 1, 3, 5), (("lstm", "gru", "lstm"), 1, 17, 4)]
-
-
-@functools.lru_cache(maxsize=None)
-def _case(mixers, r, B, T):
-    """Model, ragged batch and scheduled-sampling mask of one case, and the module path's prediction."""
-    from multimodalreactiongeneration_amd.synthetic import make_batch
-    torch.manual_seed(3)
-    m = _model(emb_mixers=mixers, ratio=r, num_block=2, encoder_num_layer=2).eval()
-    lengths = [T] * B
-    lengths[1] = T - 4
-    batch = make_batch(B=B, T=T, ratio=r, lead=12, seed=5, lengths=lengths, device=DEV)
-    mask = torch.from_numpy(np.random.RandomState(9).rand(T) < 0.5).to(DEV)
-    with torch.enable_grad():
-        slow = m._generate(batch, sampling_mask=mask).detach()
-    torch.cuda.synchronize()
-    return m, batch, mask, slow
 
 
 @pytest.mark.parametrize("mixers,r,B,T", CASES)
@@ -195,27 +137,8 @@ def test_generation_gru_fused_matches_module_path(mixers, r, B, T):
     the zero-state cell at ratio 1, as an r-step zero-state recurrence per frame above it) vs the
     per-frame module forward, ragged padding, scheduled-sampling mask."""
     from multimodalreactiongeneration_amd import _lib as L
-    from multimodalreactiongeneration_amd import functional as Fn
-    from multimodalreactiongeneration_amd import generate as G
     m, batch, mask, slow = _case(mixers, r, B, T)
-    plan = G.plan_for(m)
-    assert plan is not None
-    fast, loops = {}, {}
-    inner = plan._generate_loop
-    prev = G._LOOP[0]
-    try:
-        for loop in (True, False):
-            G._LOOP[0] = loop
-            calls = []
-            plan._generate_loop = lambda *a, **k: (calls.append(1), inner(*a, **k))[1]
-            with torch.no_grad():
-                fast[loop] = m._generate(batch, sampling_mask=mask)
-            loops[loop] = len(calls)
-    finally:
-        G._LOOP[0] = prev
-        del plan._generate_loop
-    torch.cuda.synchronize()
-    Fn.check_errors()
+    fast, loops = _fast_both_ways(m, batch, mask)
     # the one-launch loop is a ratio-1 path for an LSTM main chain, whatever the side stacks are
     fits = L.load().mrg_gen_loop_fits(B, L.cu_count(0)) == 1
     assert loops == {True: int(r == 1 and mixers[2] == "lstm" and fits), False: 0}
@@ -229,24 +152,6 @@ def test_generation_gru_fused_matches_module_path(mixers, r, B, T):
 def test_generation_gru_graph_replay():
     """gru x 3 at r = 2 captured once as a HIP graph with the mask in a device buffer, replayed for two
     masks: each replay is the eager fast path's result for its mask, bit for bit."""
-    from multimodalreactiongeneration_amd.graphs import capture
     mixers, r, B, T = CASES[2]
     m, batch, mask0, _ = _case(mixers, r, B, T)
-    masks = [mask0, ~mask0]
-    eager = []
-    with torch.no_grad():
-        for mk in masks:
-            eager.append(m._generate(batch, sampling_mask=mk).clone())
-    assert not torch.equal(eager[0], eager[1])
-    mask = torch.zeros(T, dtype=torch.bool, device=DEV)
-    out = torch.zeros(B, T, 6, device=DEV)
-
-    def gen():
-        with torch.no_grad():
-            out.copy_(m._generate(batch, sampling_mask=mask))
-    replay = capture(gen, 1)
-    for mk, want in zip(masks, eager):
-        mask.copy_(mk)
-        replay()
-        torch.cuda.synchronize()
-        assert torch.equal(out, want)
+    _graph_replay_is_eager(m, batch, mask0, B, T)
