@@ -70,6 +70,12 @@ int mrg_lstm_config(int group256);
 /* Tuning knob: members of a persistent GRU ring at H = 256 (4, default, or 8); returns the previous
  * setting.  Process-wide; set before capture, not during. */
 int mrg_gru_config(int group256);
+/* Tests: force the batch tile (rows per workgroup group) of later mrg_gru_fwd / mrg_gru_bwd launches to
+ * 1, 2, 4 or 8; 0 (default) = the first tile whose grid fits.  A forced ring tile (H = 256) must still
+ * fit the device, else the call fails with nothing launched; a forced solo tile launches regardless; a
+ * tile the width does not instantiate (8 at H = 128) is an error.  Returns the previous setting; any
+ * other value is refused (2, mrg_last_error(), the setting unchanged).  Process-wide. */
+int mrg_gru_force_tile(int bs);
 /* Solo (one-workgroup, LDS-exchange) recurrence groups at H <= 128: 1 on (default), 0 off; returns the
  * previous setting. */
 int mrg_lstm_set_solo(int on);

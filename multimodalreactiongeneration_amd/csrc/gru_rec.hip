@@ -399,6 +399,9 @@ static int gru_group(int H) {
   }
 }
 
+// batch tile forced by mrg_gru_force_tile (tests): 0 = the first that fits
+static int g_gru_force_tile = 0;
+
 // launch at batch tile BS when the grid fits the GPU at once; a solo group (no hand-offs, no
 // co-residency requirement) also launches at its last candidate tile when none fits
 template <typename K, typename A>
@@ -412,9 +415,15 @@ template <int H, int G>
 static int gru_launch_fwd(const GruFwdArgs& a, int cus, hipStream_t s) {
   constexpr int NT = GruFwdCfg<H, G>::NT;
   constexpr int BMAX = gru_tile_ok<H, G, 8>() ? 8 : gru_tile_ok<H, G, 4>() ? 4 : 2;
+  const int force = g_gru_force_tile;
+  if (force > BMAX) {
+    set_error("gru fwd: batch tile %d is not instantiated at H=%d (largest %d)", force, H, BMAX);
+    return 2;
+  }
   for (int bs = 1; bs <= BMAX; bs *= 2) {
+    if (force > 0 && bs != force) continue;   // a forced ring tile must still fit; a forced solo tile is the last
     const long nblk = (long)((a.B + bs - 1) / bs) * G;
-    const bool sl = G == 1 && bs == BMAX;
+    const bool sl = G == 1 && (bs == BMAX || bs == force);
     bool ok = false;
     switch (bs) {
       case 1: ok = gru_try(gru_fwd_kernel<H, G, 1>, NT, nblk, cus, sl, s, a); break;
@@ -424,7 +433,7 @@ static int gru_launch_fwd(const GruFwdArgs& a, int cus, hipStream_t s) {
     }
     if (ok) return check_launch("gru_fwd_kernel");
   }
-  set_error("gru fwd: persistent grid does not fit the GPU (B=%d H=%d)", a.B, H);
+  set_error("gru fwd: persistent grid does not fit the GPU (B=%d H=%d force_tile=%d)", a.B, H, force);
   return 4;
 }
 
@@ -432,9 +441,15 @@ template <int H, int G>
 static int gru_launch_bwd(const GruBwdArgs& a, int cus, hipStream_t s) {
   constexpr int NT = GruBwdCfg<H, G>::NT;
   constexpr int BMAX = gru_tile_ok<H, G, 8>() ? 8 : gru_tile_ok<H, G, 4>() ? 4 : 2;
+  const int force = g_gru_force_tile;
+  if (force > BMAX) {
+    set_error("gru bwd: batch tile %d is not instantiated at H=%d (largest %d)", force, H, BMAX);
+    return 2;
+  }
   for (int bs = 1; bs <= BMAX; bs *= 2) {
+    if (force > 0 && bs != force) continue;   // a forced ring tile must still fit; a forced solo tile is the last
     const long nblk = (long)((a.B + bs - 1) / bs) * G;
-    const bool sl = G == 1 && bs == BMAX;
+    const bool sl = G == 1 && (bs == BMAX || bs == force);
     bool ok = false;
     switch (bs) {
       case 1: ok = gru_try(gru_bwd_kernel<H, G, 1>, NT, nblk, cus, sl, s, a); break;
@@ -444,7 +459,7 @@ static int gru_launch_bwd(const GruBwdArgs& a, int cus, hipStream_t s) {
     }
     if (ok) return check_launch("gru_bwd_kernel");
   }
-  set_error("gru bwd: persistent grid does not fit the GPU (B=%d H=%d)", a.B, H);
+  set_error("gru bwd: persistent grid does not fit the GPU (B=%d H=%d force_tile=%d)", a.B, H, force);
   return 4;
 }
 
@@ -458,6 +473,13 @@ MRG_API int mrg_gru_config(int group256) {
   MRG_REQUIRE(group256 == 4 || group256 == 8, "mrg_gru_config: group must be 4 or 8");
   const int prev = g_gru_group256;
   g_gru_group256 = group256;
+  return prev;
+}
+
+MRG_API int mrg_gru_force_tile(int bs) {
+  MRG_REQUIRE(bs == 0 || bs == 1 || bs == 2 || bs == 4 || bs == 8, "mrg_gru_force_tile: tile must be 0, 1, 2, 4 or 8");
+  const int prev = g_gru_force_tile;
+  g_gru_force_tile = bs;
   return prev;
 }
 

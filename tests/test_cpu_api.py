@@ -35,7 +35,7 @@ def test_boundary_header_holds_no_tuning_hooks():
     tuning = set(_header_functions(("mrg_tuning.h",)))
     assert not boundary & tuning
     for name in ("mrg_gemm_x6_variant", "mrg_gemm_force_tile", "mrg_ssd_gate_cell_fwd_dbg", "mrg_gemm_set_wide",
-                 "mrg_lstm_debug_inject", "mrg_lstm_debug_stamps", "mrg_probe_start"):
+                 "mrg_lstm_debug_inject", "mrg_lstm_debug_stamps", "mrg_probe_start", "mrg_gru_force_tile"):
         assert name in tuning and name not in boundary, name
     for name in ("mrg_split_planes_batched", "mrg_gemm_x6_planes", "mrg_gemm_x6_planes_batched"):
         assert name in boundary, name
@@ -64,6 +64,11 @@ def test_workspace_size_helpers():
     assert lib.mrg_lstm_fwd_xbuf_bytes(64, 256) == 2 * 64 * 256 * 8
     assert lib.mrg_lstm_bwd_xbuf_bytes(64, 256) == 2 * 64 * 16 * 256 * 8
     assert lib.mrg_attention_bwd_workspace_bytes(2, 4, 300) == 2 * 4 * 300 * 4
+    # the GRU ring: [2][B][G][H] granules at the largest ring a launch may take (8 at H = 256, solo below;
+    # an unsupported width as a solo group)
+    assert lib.mrg_gru_xbuf_bytes(64, 256) == 2 * 64 * 8 * 256 * 8
+    assert lib.mrg_gru_xbuf_bytes(64, 128) == 2 * 64 * 128 * 8
+    assert lib.mrg_gru_xbuf_bytes(64, 12) == 2 * 64 * 12 * 8
 
 
 @pytest.mark.parametrize("name,builder", [("Metaformer", "lstmformer_config"),
