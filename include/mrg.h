@@ -620,6 +620,22 @@ int mrg_grad_clip_norm(float* grads, long n, float max_norm, float* clip_state, 
                        hipStream_t stream);
 int mrg_grad_clip_value(float* grads, long n, float clip_value, hipStream_t stream);
 
+/* ---------------------------------------------------------------- level schedule frame moves
+ * Scheduled-sampling training of the lstmformer in dependence levels (ss_levels.py).  Tensors are
+ * time-major, a frame is one [B][W] slab; idx / prev / teacher are device int32 [n].
+ *   mrg_frame_gather   dst[i]      = src[idx[i]]        (idx may repeat)
+ *   mrg_frame_scatter  dst[idx[i]] = src[i]             (idx distinct: one writer per slab)
+ *   mrg_level_input    dst[i]      = prev[i] >= 0 ? y_prev[prev[i]] : ms[teacher[i]]
+ * In mrg_level_input a null y_prev reads every slab from ms, and a null ms (teacher then unused)
+ * writes zeros where prev[i] < 0: with the inverse map for prev that is the gradient with respect
+ * to y_prev.  The indices are not range-checked on the device: the caller owns that.  One launch
+ * each, plain stores, no atomics; float4 when W % 4 == 0 and every base is 16-byte aligned, else
+ * float by float.  n == 0 (or B * W == 0) launches nothing.                                     */
+int mrg_frame_gather(int n, int B, int W, const float* src, const int* idx, float* dst, hipStream_t stream);
+int mrg_frame_scatter(int n, int B, int W, const float* src, const int* idx, float* dst, hipStream_t stream);
+int mrg_level_input(int n, int B, int W, const float* y_prev, const int* prev, const float* ms,
+                    const int* teacher, float* dst, hipStream_t stream);
+
 /* ---------------------------------------------------------------- features (data loader)
  * AudioPreprocessor (mr_gen/utils/preprocess/audio.py:6-67).  The power spectrum comes from one
  * GEMM of the frames (read in place from the waveform, row stride `hop`) with the windowed DFT

@@ -199,6 +199,9 @@ SIGNATURES = {
     "mrg_grad_clip_workspace_bytes": (c_size, [c_long]),
     "mrg_grad_clip_norm": (c_int, [P, c_long, c_float, P, P, P]),
     "mrg_grad_clip_value": (c_int, [P, c_long, c_float, P]),
+    "mrg_frame_gather": (c_int, [c_int, c_int, c_int, P, P, P, P]),
+    "mrg_frame_scatter": (c_int, [c_int, c_int, c_int, P, P, P, P]),
+    "mrg_level_input": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P]),
     "mrg_lstm_debug_inject": (c_int, [c_int]),
     "mrg_comm_available": (c_int, []),
     "mrg_comm_id_bytes": (c_size, []),

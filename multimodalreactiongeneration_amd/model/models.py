@@ -160,6 +160,12 @@ class _TorchLoss(nn.Module):
 class Metaformer(LightningSurface):
     """LSTM + cross-modal attention metaformer (lstmformer.py:70-559)."""
 
+    # scheduled-sampling training runs the frames of one dependence depth as one forward (ss_levels.py);
+    # False, or MRG_SS_LEVELS=0, keeps one forward per frame
+    use_level_schedule = os.environ.get("MRG_SS_LEVELS", "1") == "1"
+    # set by the level schedule around its forwards: it has prepared the step's weight planes already
+    _planes_prepared = False
+
     def __init__(self, model, optim, metrics):
         super().__init__()
         model, optim, metrics = as_attr(model), as_attr(optim), as_attr(metrics)
@@ -247,7 +253,7 @@ class Metaformer(LightningSurface):
         mp = _cat_lead(leading_motion_partner[0].to(dev), motion_partner[0].to(dev))
         ms = _cat_lead(leading_motion_self[0].to(dev), motion_self[0].to(dev))
         T = mp.shape[1]
-        if torch.is_grad_enabled() and mp.shape[0] * T >= 2048:
+        if torch.is_grad_enabled() and mp.shape[0] * T >= 2048 and not self._planes_prepared:
             # a training forward over whole sequences: the bf16 planes of every weight, once per step
             # (functional.prepare_weight_planes; per-frame decode forwards keep the step's planes)
             Fn.prepare_weight_planes(self.parameters())
@@ -367,7 +373,17 @@ class Metaformer(LightningSurface):
             plan = plan_for(self)
             if plan is not None:
                 return plan.generate(fb, mp, ms, mask)
-        empty = [(torch.empty(x.shape[0], 0, x.shape[2], device=dev), n) for x, n in batch]
+        elif self.use_level_schedule and mask.device.type == "cpu":
+            # training: the frames of one dependence depth as one forward (ss_levels.py).  A device mask
+            # (HIP-graph capture), an active dropout (one draw per frame forward) and a plan that saves no
+            # forward (an all-sampled mask) keep the loop below.
+            from .. import ss_levels
+            from ..generate import _dropout_active
+            if not _dropout_active(self.metaformer):
+                levels = ss_levels.plan_levels(mask, ss_levels.rows_cap_for(self, dev), B)
+                if len(levels) < T:
+                    return ss_levels.generate_levels(self, fb, mp, ms, mask, levels)
+        empty =[(torch.empty(x.shape[0], 0, x.shape[2], device=dev), n) for x, n in batch]
         _, cell = self.forward(*empty[:3], *batch[3:6], hxs=None)
         on_device = mask.device.type != "cpu"
         y = ms[0]
