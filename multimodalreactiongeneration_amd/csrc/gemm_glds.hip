@@ -1,6 +1,7 @@
 // x6 GEMM with LDS-DMA staging (gfx950 global_load_lds_dwordx4): see the comment below.
 #include "gemm_common.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace mrg {
 MRG_EPI_NS_BEGIN
@@ -99,6 +100,34 @@ __device__ __forceinline__ f32x16 mfma_planes(const bf16x8 (&b)[NP], const bf16x
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[0], a[1], acc, 0, 0, 0);
   }
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[0], a[0], acc, 0, 0, 0);
+}
+
+// product p of mfma_planes' sequence on its own (NP = 3: six, small terms first; NP = 1: one)
+template <int NP>
+__device__ __forceinline__ f32x16 mfma_term(int p, const bf16x8 (&b)[NP], const bf16x8 (&a)[NP], f32x16 acc) {
+  if constexpr (NP == 3) {
+    constexpr int ib[6] = {2, 1, 0, 1, 0, 0}, ia[6] = {0, 1, 2, 0, 1, 0};
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[ib[p]], a[ia[p]], acc, 0, 0, 0);
+  }
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[0], a[0], acc, 0, 0, 0);
+}
+
+// counted wait on the untracked LDS reads, tied to the eight registers of the fragment it makes
+// valid: their users cannot be scheduled above it
+template <int N>
+__device__ __forceinline__ void lgkm_wait8(float (&v)[8]) {
+  asm volatile("s_waitcnt lgkmcnt(%8)"
+               : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7])
+               : "n"(N)
+               : "memory");
+}
+
+// no instruction: marks the planes as used here, so that the code computing them is not sunk into
+// the block of their first MFMA
+template <int NP>
+__device__ __forceinline__ void pin_planes(bf16x8 (&f)[NP]) {
+#pragma unroll
+  for (int p = 0; p < NP; ++p) asm volatile("" : "+v"(f[p]));
 }
 
 template <int N>
@@ -354,32 +383,34 @@ __device__ __forceinline__ void wgrad_tile(const GemmArgs& a, int t, unsigned ch
   const int kbeg = z * a.kchunk, kend = min(a.K, kbeg + a.kchunk);
   const int nk = (kend - kbeg) / 32;
 
+  // a plain row stride (no RowMap division): the lane's own k-row offset folds into src once, and a
+  // k-tile adds one wave-uniform offset
+  const bool lin_a = a.amap.rdiv <= 0, lin_b = a.bmap.rdiv <= 0;
   const float* src[GT];
-  long rstep[GT];  // not used: rows advance through the RowMap per k-tile
   int kk[GT], dsto[GT];
 #pragma unroll
   for (int g = 0; g < GT; ++g) {
     if (g < GA) {
       const int grp = wave * GA + g, k = grp * RA + lane / (BM / 4), c = lane % (BM / 4);
       const int chunk = c ^ (((k >> 3) & 1) << 3);
-      src[g] = a.A + min(m0 + 4 * chunk, a.M - 4);
+      src[g] = a.A + min(m0 + 4 * chunk, a.M - 4) + (lin_a ? (long)k * a.amap.ld_lo : 0L);
       kk[g] = k;
       dsto[g] = grp << 10;
     } else {
       const int grp = wave * GB + (g - GA), k = grp * RB + lane / (BN / 4), c = lane % (BN / 4);
       const int chunk = c ^ (((k >> 3) & 1) << 3);
-      src[g] = a.B + min(n0 + 4 * chunk, a.N - 4);
+      src[g] = a.B + min(n0 + 4 * chunk, a.N - 4) + (lin_b ? (long)k * a.bmap.ld_lo : 0L);
       kk[g] = k;
       dsto[g] = SA + (grp << 10);
     }
-    rstep[g] = 0;
   }
-  (void)rstep;
   auto issue = [&](int kt, int slot) {
+    const int k0 = kbeg + kt * 32;
+    const long ua = (long)k0 * a.amap.ld_lo, ub = (long)k0 * a.bmap.ld_lo;
 #pragma unroll
     for (int g = 0; g < GT; ++g) {
-      const int k = kbeg + kt * 32 + kk[g];
-      const float* p = src[g] + (g < GA ? a.amap.off(k) : a.bmap.off(k));
+      const float* p = g < GA ? src[g] + (lin_a ? ua : a.amap.off(k0 + kk[g]))
+                              : src[g] + (lin_b ? ub : a.bmap.off(k0 + kk[g]));
       __builtin_amdgcn_global_load_lds((const void*)p, (__attribute__((address_space(3))) void*)(lds + slot * SS + dsto[g]),
                                        16, 0, 0);
     }
@@ -409,49 +440,104 @@ __device__ __forceinline__ void wgrad_tile(const GemmArgs& a, int t, unsigned ch
     ob[jj] = SA + wg_off<BN>(8 * lh, n >> 2) + 4 * (n & 3);
   }
 
+  // Schedule of the k loop (one wave per SIMD, so nothing else hides a wave's own stalls): half
+  // k-step h's MFMAs run on planes split during half-step h - 1, and between them the wave reads
+  // half-step h + 1's fragments (two in flight, counted waits at each fragment's first use) and
+  // splits them into the other plane set: the MFMA pipe and the VALU work side by side.  The
+  // products and their order per accumulator are those of mfma_planes.
+  constexpr int F = TM + TN, NMF = NP == 3 ? 6 : 1, G = TM * TN * NMF;
+  constexpr int LEAD = G / (F + 1);     // MFMAs ahead of the first wait (they cover the read latency)
+  constexpr int VPM = NP == 3 ? 9 : 6;  // VALU instructions of the split scheduled behind each MFMA
+  float raw[F][8];
+  bf16x8 fa[2][TM][NP], fb[2][TN][NP];
+  auto read_frag = [&](auto s_, int q, unsigned sa) {  // fragment q of half s of the slot at sa -> raw[q]
+    constexpr int K0 = 16 * decltype(s_)::value;
+    if (q < TM) lds_read8k<BM * 4, K0>(sa + oa[q < TM ? q : 0], raw[q]);
+    else lds_read8k<BN * 4, K0>(sa + ob[q < TM ? 0 : q - TM], raw[q]);
+  };
+  auto split_frag = [&](int q, int d) {  // raw[q] -> plane set d (and the fused row sums)
+    const float(&v)[8] = raw[q];
+    const f32x4v_ v0 = {v[0], v[1], v[2], v[3]}, v1 = {v[4], v[5], v[6], v[7]};
+    if (q < TM) {
+      const int i = q < TM ? q : 0;
+      // every wave sums (a branch here would cut the MFMA / VALU interleave); do_asum waves store
+      cs[i] += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+      planes8<NP>(v0, v1, fa[d][i]);
+    } else {
+      planes8<NP>(v0, v1, fb[d][q < TM ? 0 : q - TM]);
+    }
+  };
+  auto mfmas = [&](int c, int lo, int hi) {  // products lo..hi - 1 of a half-step's G, on plane set c
 #pragma unroll
-  for (int st = 0; st < NS - 1; ++st)
-    if (st < nk) issue(st, st);
-  for (int kt = 0; kt < nk; ++kt) {
+    for (int e = 0; e < G; ++e)
+      if (e >= lo && e < hi) {
+        const int g = e / NMF, i = g / TN, j = g % TN;
+        acc[i][j] = mfma_term<NP>(e % NMF, fb[c][j], fa[c][i], acc[i][j]);
+      }
+  };
+  // wait for k-tile kt's DMA, make it visible, and refill the slot the workgroup read last
+  auto enter = [&](int kt) {
     const int ahead = min(NS - 2, nk - 1 - kt);
     if (ahead >= 2) vm_wait<2 * GT>();
     else if (ahead == 1) vm_wait<GT>();
     else vm_wait<0>();
     __builtin_amdgcn_s_barrier();
     if (kt + NS - 1 < nk) issue(kt + NS - 1, (kt + NS - 1) % NS);
-    const unsigned sa = lds_base + (kt % NS) * SS;
+  };
+  // the MFMAs of plane set c beside the reads and the split of the following half-step (half
+  // 1 - c of the slot at sn) into set 1 - c
+  auto half = [&](auto c_, unsigned sn) {
+    constexpr int c = decltype(c_)::value, d = 1 - c;
+    const std::integral_constant<int, d> d_;
+    read_frag(d_, 0, sn);
+    read_frag(d_, 1, sn);
+    __builtin_amdgcn_sched_barrier(0);
+    mfmas(c, 0, LEAD);
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      float va[TM][8], vb[TN][8];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        if (s == 0) lds_read8k<BM * 4, 0>(sa + oa[i], va[i]);
-        else lds_read8k<BM * 4, 16>(sa + oa[i], va[i]);
-      }
-#pragma unroll
-      for (int jj = 0; jj < TN; ++jj) {
-        if (s == 0) lds_read8k<BN * 4, 0>(sa + ob[jj], vb[jj]);
-        else lds_read8k<BN * 4, 16>(sa + ob[jj], vb[jj]);
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    for (int q = 0; q < F; ++q) {
       __builtin_amdgcn_sched_barrier(0);
-      bf16x8 fa[TM][NP], fb[TN][NP];
+      if (q + 1 < F) lgkm_wait8<8>(raw[q]);  // fragment q + 1 stays in flight
+      else lgkm_wait8<0>(raw[q]);
+      if (q + 2 < F) read_frag(d_, q + 2, sn);
+      split_frag(q, d);
+      const int lo = LEAD + q * (G - LEAD) / F, hi = LEAD + (q + 1) * (G - LEAD) / F;
+      mfmas(c, lo, hi);
 #pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        if (do_asum)
-          cs[i] += ((va[i][0] + va[i][1]) + (va[i][2] + va[i][3])) + ((va[i][4] + va[i][5]) + (va[i][6] + va[i][7]));
-        planes8<NP>(f32x4v_{va[i][0], va[i][1], va[i][2], va[i][3]}, f32x4v_{va[i][4], va[i][5], va[i][6], va[i][7]},
-                    fa[i]);
-      }
-#pragma unroll
-      for (int jj = 0; jj < TN; ++jj)
-        planes8<NP>(f32x4v_{vb[jj][0], vb[jj][1], vb[jj][2], vb[jj][3]},
-                    f32x4v_{vb[jj][4], vb[jj][5], vb[jj][6], vb[jj][7]}, fb[jj]);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = mfma_planes<NP>(fb[j], fa[i], acc[i][j]);
+      for (int e = 0; e < G; ++e)
+        if (e >= lo && e < hi) {
+          __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);    // one MFMA,
+          __builtin_amdgcn_sched_group_barrier(0x2, VPM, 0);  // then VALU of the split in its shadow
+        }
+      // the planes are first used past the next barrier: keep their split here, beside these MFMAs
+      if (q < TM) pin_planes<NP>(fa[d][q < TM ? q : 0]);
+      else pin_planes<NP>(fb[d][q < TM ? 0 : q - TM]);
     }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  const std::integral_constant<int, 0> c0;
+  const std::integral_constant<int, 1> c1;
+
+#pragma unroll
+  for (int st = 0; st < NS - 1; ++st)
+    if (st < nk) issue(st, st);
+  if (nk > 0) {  // prologue: the first half-step's planes, with nothing to run beside
+    enter(0);
+#pragma unroll
+    for (int q = 0; q < F; ++q) read_frag(c0, q, lds_base);
+#pragma unroll
+    for (int q = 0; q < F; ++q) {
+      lgkm_wait8<0>(raw[q]);
+      split_frag(q, 0);
+    }
+  }
+  for (int kt = 0; kt + 1 < nk; ++kt) {
+    half(c0, lds_base + (kt % NS) * SS);
+    enter(kt + 1);
+    half(c1, lds_base + ((kt + 1) % NS) * SS);
+  }
+  if (nk > 0) {  // the last k-tile: nothing follows its second half
+    half(c0, lds_base + ((nk - 1) % NS) * SS);
+    mfmas(1, 0, G);
   }
   if (do_asum) {  // lanes l and l + 32 hold the two k halves of row m = wm + 32 i + (l & 31)
 #pragma unroll
@@ -465,8 +551,9 @@ __device__ __forceinline__ void wgrad_tile(const GemmArgs& a, int t, unsigned ch
   if constexpr (BN >= 128) {
     constexpr int WC = TN * 32, PITCH = WC + 4, C4 = WC / 4;
     float* stg = reinterpret_cast<float*>(lds) + wave * 32 * PITCH;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
+    // the row block i as a constant (not a loop the compiler may leave rolled: acc stays in registers)
+    auto stage = [&](auto i_) {
+      constexpr int i = decltype(i_)::value;
 #pragma unroll
       for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -484,7 +571,9 @@ __device__ __forceinline__ void wgrad_tile(const GemmArgs& a, int t, unsigned ch
       }
       __builtin_amdgcn_wave_barrier();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
+    };
+    stage(c0);
+    if constexpr (TM > 1) stage(c1);
   } else {
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
