@@ -966,10 +966,7 @@ static AttnArgs attn_base(int B, int Hh, int Tq, int Tk, const float* q, long q_
 
 // single-pass backward (attn_bwd_fused_kernel) where it applies: 1 (default) or 0 (MRG_ATTN_FUSED,
 // mrg_attention_set_fused: the two-pass form always)
-static int g_attn_fused = [] {
-  const char* e = getenv("MRG_ATTN_FUSED");
-  return e ? atoi(e) : 1;
-}();
+static int g_attn_fused = env_int("MRG_ATTN_FUSED", 1);
 
 MRG_API int mrg_attention_set_fused(int on) {
   const int prev = g_attn_fused;

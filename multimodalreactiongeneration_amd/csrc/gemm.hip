@@ -881,25 +881,15 @@ MRG_EPI_NS_END
 MRG_KNOB(g_tile_override, -1);
 // LDS-DMA x6 kernel for k-contiguous products (gemm_x6g_kernel): 0 = off, else ring depth (2..4);
 // MRG_GEMM_GLDS overrides; g_glds_bn = column tile (128 or 64)
-MRG_KNOB(g_glds, [] {
-  const char* e = getenv("MRG_GEMM_GLDS");
-  return e ? atoi(e) : 2;
-}());
-MRG_KNOB(g_glds_wg, [] {  // weight-gradient products on gemm_x6g_wgrad_kernel (MRG_GEMM_GLDS_WG=0: off)
-  const char* e = getenv("MRG_GEMM_GLDS_WG");
-  return e ? atoi(e) : 1;
-}());
-MRG_KNOB(g_glds_bn, [] {  // 64 forces 64-wide column tiles (tuning); 128 = by shape
-  const char* e = getenv("MRG_GEMM_GLDS_BN");
-  return e ? atoi(e) : 128;
-}());
+MRG_KNOB(g_glds, env_int("MRG_GEMM_GLDS", 2));
+// weight-gradient products on gemm_x6g_wgrad_kernel (MRG_GEMM_GLDS_WG=0: off)
+MRG_KNOB(g_glds_wg, env_int("MRG_GEMM_GLDS_WG", 1));
+// 64 forces 64-wide column tiles (tuning); 128 = by shape
+MRG_KNOB(g_glds_bn, env_int("MRG_GEMM_GLDS_BN", 128));
 
 
 // GEMM arithmetic: 1 = x6 bf16 split on the bf16 matrix cores (default), 0 = exact f32 MFMA
-MRG_KNOB(g_gemm_mode, [] {
-  const char* e = getenv("MRG_GEMM_EXACT");
-  return (e && atoi(e) != 0) ? 0 : 1;
-}());
+MRG_KNOB(g_gemm_mode, env_int("MRG_GEMM_EXACT", 0) != 0 ? 0 : 1);
 
 MRG_EPI_NS_BEGIN
 

@@ -715,8 +715,7 @@ using namespace mrg;
 extern int g_wide_cfg;
 #else
 int g_wide_cfg = [] {
-  const char* e = getenv("MRG_GEMM_WIDE");
-  const int v = e ? atoi(e) : 12;
+  const int v = env_int("MRG_GEMM_WIDE", 12);
   return (v == 0 || v == 22) ? v : 12;
 }();
 #endif

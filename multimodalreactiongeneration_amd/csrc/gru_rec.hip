@@ -14,6 +14,7 @@
 // a member's partial dh_{t-1} = dgh(own rows) W_hh(own rows, :) is reduce-scattered like the LSTM's,
 // and each cell adds its direct term dh_t z_t.  Outputs match the per-step path (gru.hip): y, gates
 // (r, z, n), ghn = W_hn h + b_hn, and dGX / dGH for the weight / input gradient GEMMs.
+// The host's walk over the batch tiles is the LSTM's (launch_tiles, lstm_common.h).
 #include "lstm_common.h"
 
 namespace mrg {
@@ -386,10 +387,7 @@ __global__ __launch_bounds__((GruBwdCfg<H, G>::NT), (GruBwdCfg<H, G>::WPS)) void
 // ring size at H = 256: 4 members (U = 64, 768 / 512 threads) by default, measured 0.7-1.0 ms faster
 // on the GRU config than 8 (U = 32; profiles/r04_gru_persistent.txt); MRG_GRU_GROUP256=8 or
 // mrg_gru_config(8) selects 8
-static int g_gru_group256 = [] {
-  const char* e = getenv("MRG_GRU_GROUP256");
-  return (e && atoi(e) == 8) ? 8 : 4;
-}();
+static int g_gru_group256 = env_int("MRG_GRU_GROUP256", 4) == 8 ? 8 : 4;
 
 static int gru_group(int H) {
   switch (H) {
@@ -402,66 +400,30 @@ static int gru_group(int H) {
 // batch tile forced by mrg_gru_force_tile (tests): 0 = the first that fits
 static int g_gru_force_tile = 0;
 
-// launch at batch tile BS when the grid fits the GPU at once; a solo group (no hand-offs, no
-// co-residency requirement) also launches at its last candidate tile when none fits
-template <typename K, typename A>
-static bool gru_try(K kernel, int nt, long nblk, int cus, bool solo_last, hipStream_t s, const A& a) {
-  if (!fits(kernel, nt, nblk, cus) && !solo_last) return false;
-  klaunch(kernel, nblk, nt, 0, s, a);
-  return true;
-}
-
-template <int H, int G>
-static int gru_launch_fwd(const GruFwdArgs& a, int cus, hipStream_t s) {
-  constexpr int NT = GruFwdCfg<H, G>::NT;
-  constexpr int BMAX = gru_tile_ok<H, G, 8>() ? 8 : gru_tile_ok<H, G, 4>() ? 4 : 2;
-  const int force = g_gru_force_tile;
-  if (force > BMAX) {
-    set_error("gru fwd: batch tile %d is not instantiated at H=%d (largest %d)", force, H, BMAX);
-    return 2;
+// kernel families of launch_tiles (lstm_common.h): the launch must be wholly resident, or the last
+// candidate of a solo group; batch tiles up to 8
+template <int H, int G, bool BWD>
+struct GruTiles {
+  static constexpr int NT = BWD ? GruBwdCfg<H, G>::NT : GruFwdCfg<H, G>::NT, BCAP = 8;
+  static constexpr const char* name = BWD ? "gru_bwd_kernel" : "gru_fwd_kernel";
+  template <int BS>
+  static constexpr bool ok() { return gru_tile_ok<H, G, BS>(); }
+  template <int BS>
+  static auto kernel() {
+    if constexpr (BWD) return gru_bwd_kernel<H, G, BS>;
+    else return gru_fwd_kernel<H, G, BS>;
   }
-  for (int bs = 1; bs <= BMAX; bs *= 2) {
-    if (force > 0 && bs != force) continue;   // a forced ring tile must still fit; a forced solo tile is the last
-    const long nblk = (long)((a.B + bs - 1) / bs) * G;
-    const bool sl = G == 1 && (bs == BMAX || bs == force);
-    bool ok = false;
-    switch (bs) {
-      case 1: ok = gru_try(gru_fwd_kernel<H, G, 1>, NT, nblk, cus, sl, s, a); break;
-      case 2: ok = gru_try(gru_fwd_kernel<H, G, 2>, NT, nblk, cus, sl, s, a); break;
-      case 4: if constexpr (gru_tile_ok<H, G, 4>()) ok = gru_try(gru_fwd_kernel<H, G, 4>, NT, nblk, cus, sl, s, a); break;
-      default: if constexpr (gru_tile_ok<H, G, 8>()) ok = gru_try(gru_fwd_kernel<H, G, 8>, NT, nblk, cus, sl, s, a); break;
+  template <typename Args>
+  static int no_fit(const Args& a, int force, int bmax) {
+    const char* dir = BWD ? "bwd" : "fwd";
+    if (force > bmax) {
+      set_error("gru %s: batch tile %d is not instantiated at H=%d (largest %d)", dir, force, H, bmax);
+      return 2;
     }
-    if (ok) return check_launch("gru_fwd_kernel");
+    set_error("gru %s: persistent grid does not fit the GPU (B=%d H=%d force_tile=%d)", dir, a.B, H, force);
+    return 4;
   }
-  set_error("gru fwd: persistent grid does not fit the GPU (B=%d H=%d force_tile=%d)", a.B, H, force);
-  return 4;
-}
-
-template <int H, int G>
-static int gru_launch_bwd(const GruBwdArgs& a, int cus, hipStream_t s) {
-  constexpr int NT = GruBwdCfg<H, G>::NT;
-  constexpr int BMAX = gru_tile_ok<H, G, 8>() ? 8 : gru_tile_ok<H, G, 4>() ? 4 : 2;
-  const int force = g_gru_force_tile;
-  if (force > BMAX) {
-    set_error("gru bwd: batch tile %d is not instantiated at H=%d (largest %d)", force, H, BMAX);
-    return 2;
-  }
-  for (int bs = 1; bs <= BMAX; bs *= 2) {
-    if (force > 0 && bs != force) continue;   // a forced ring tile must still fit; a forced solo tile is the last
-    const long nblk = (long)((a.B + bs - 1) / bs) * G;
-    const bool sl = G == 1 && (bs == BMAX || bs == force);
-    bool ok = false;
-    switch (bs) {
-      case 1: ok = gru_try(gru_bwd_kernel<H, G, 1>, NT, nblk, cus, sl, s, a); break;
-      case 2: ok = gru_try(gru_bwd_kernel<H, G, 2>, NT, nblk, cus, sl, s, a); break;
-      case 4: if constexpr (gru_tile_ok<H, G, 4>()) ok = gru_try(gru_bwd_kernel<H, G, 4>, NT, nblk, cus, sl, s, a); break;
-      default: if constexpr (gru_tile_ok<H, G, 8>()) ok = gru_try(gru_bwd_kernel<H, G, 8>, NT, nblk, cus, sl, s, a); break;
-    }
-    if (ok) return check_launch("gru_bwd_kernel");
-  }
-  set_error("gru bwd: persistent grid does not fit the GPU (B=%d H=%d force_tile=%d)", a.B, H, force);
-  return 4;
-}
+};
 
 }  // namespace mrg
 
@@ -504,11 +466,12 @@ MRG_API int mrg_gru_fwd(int B, int T, int H, const float* gx, long gx_bs, long g
   a.ghn = ghn; a.n_bs = n_bs; a.n_ts = n_ts; a.xbuf = (unsigned long long*)xbuf;
   a.B = B; a.T = T; a.reverse = reverse ? 1 : 0; a.local = 1; a.err = err;
   if (cus <= 0) cus = device_cus();
+  auto go = [&](auto f) { return launch_tiles<decltype(f)>(a, 1, B, G, cus, g_gru_force_tile, stream); };
   switch (H) {
-    case 256: return G == 4 ? gru_launch_fwd<256, 4>(a, cus, stream) : gru_launch_fwd<256, 8>(a, cus, stream);
-    case 128: return gru_launch_fwd<128, 1>(a, cus, stream);
-    case 64: return gru_launch_fwd<64, 1>(a, cus, stream);
-    default: return gru_launch_fwd<32, 1>(a, cus, stream);
+    case 256: return G == 4 ? go(GruTiles<256, 4, false>{}) : go(GruTiles<256, 8, false>{});
+    case 128: return go(GruTiles<128, 1, false>{});
+    case 64: return go(GruTiles<64, 1, false>{});
+    default: return go(GruTiles<32, 1, false>{});
   }
 }
 
@@ -527,10 +490,11 @@ MRG_API int mrg_gru_bwd(int B, int T, int H, const float* w_hh, const float* gat
   a.dgx = dgx; a.dgh = dgh; a.d_bs = d_bs; a.d_ts = d_ts; a.dh0 = dh0; a.xbuf = (unsigned long long*)xbuf;
   a.B = B; a.T = T; a.reverse = reverse ? 1 : 0; a.local = 1; a.err = err;
   if (cus <= 0) cus = device_cus();
+  auto go = [&](auto f) { return launch_tiles<decltype(f)>(a, 1, B, G, cus, g_gru_force_tile, stream); };
   switch (H) {
-    case 256: return G == 4 ? gru_launch_bwd<256, 4>(a, cus, stream) : gru_launch_bwd<256, 8>(a, cus, stream);
-    case 128: return gru_launch_bwd<128, 1>(a, cus, stream);
-    case 64: return gru_launch_bwd<64, 1>(a, cus, stream);
-    default: return gru_launch_bwd<32, 1>(a, cus, stream);
+    case 256: return G == 4 ? go(GruTiles<256, 4, true>{}) : go(GruTiles<256, 8, true>{});
+    case 128: return go(GruTiles<128, 1, true>{});
+    case 64: return go(GruTiles<64, 1, true>{});
+    default: return go(GruTiles<32, 1, true>{});
   }
 }

@@ -2,7 +2,7 @@
 // lowers to in the reference: LSTMMixer mixer_block.py:237-252, LSTMModule
 // lstm_block.py:21-46, LSTMSampler lstm_sampler.py:16-34).
 //
-// Split of the work (host side, multimodalreactiongeneration_amd/functional.py):
+// Split of the work (host side, multimodalreactiongeneration_amd/recurrent.py over gemm_ops.py):
 //   Gx = X W_ih^T + b_ih            MFMA GEMM over all B*T rows   (gemm.hip)
 //   recurrence over t               THIS FILE, one launch per layer (or per
 //                                   batch of independent same-shape layers)
@@ -38,8 +38,11 @@
 // P_j[b][:] = dG_j[b] W_hh[rows_j, :] over ALL H outputs; the exchange is a
 // reduce-scatter (each member sums the G partials of its own units), so the
 // bytes moved per step equal the forward's (BS x H granules per member).
+//
+// Host side: the walk over the batch tiles (which tile's grid is wholly resident, the solo groups' last
+// candidate, forced tiles) is launch_tiles in lstm_common.h, shared with the GRU recurrence (gru_rec.hip);
+// this file keeps the kernels, the choice between the VALU and the MFMA form and the entry points.
 #include "lstm_common.h"
-#include <cstdlib>
 
 namespace mrg {
 
@@ -452,129 +455,59 @@ int launch_bwd_mx(const LstmBwdArgs& a, int cus, hipStream_t s);
 
 // MFMA form of the recurrence (lstm_mx.hip, H = 256, 8 members per group, batch tiles of 16):
 // 0 = never, 1 = when the VALU form would need batch tiles >= MX_MIN_BS (default), 2 = whenever it fits
-static int g_mx = [] {
-  const char* e = getenv("MRG_LSTM_MX");
-  return e ? atoi(e) : 1;
-}();
-static int g_mx_min_bs = [] {
-  const char* e = getenv("MRG_LSTM_MX_MIN_BS");
-  return e ? atoi(e) : 4;
-}();
+static int g_mx = env_int("MRG_LSTM_MX", 1);
+static int g_mx_min_bs = env_int("MRG_LSTM_MX_MIN_BS", 4);
 // the backward's own threshold (MRG_LSTM_MX_MIN_BS_BWD, default: the forward's)
-static int g_mx_min_bs_bwd = [] {
-  const char* e = getenv("MRG_LSTM_MX_MIN_BS_BWD");
-  return e ? atoi(e) : 0;
-}();
-
-// batch tile the VALU launchers would pick (smallest fitting; 0 = none fits)
-template <typename K1, typename K2, typename K4, typename K8, typename K16>
-static int valu_bs(K1 k1, K2 k2, K4 k4, K8 k8, K16 k16, int nt, int nprob, int B, int G, int cus) {
-  for (int bs = 1; bs <= 16; bs *= 2) {
-    const long nblk = (long)nprob * ((B + bs - 1) / bs) * G;
-    const bool ok = bs == 1 ? fits(k1, nt, nblk, cus) : bs == 2 ? fits(k2, nt, nblk, cus)
-                  : bs == 4 ? fits(k4, nt, nblk, cus) : bs == 8 ? fits(k8, nt, nblk, cus) : fits(k16, nt, nblk, cus);
-    if (ok) return bs;
-  }
-  return 0;
-}
-
-// one candidate batch tile: launch when it fits (or, for a solo group, when it is the last candidate:
-// its workgroups never wait on each other, so a grid larger than the GPU still completes)
-template <int BS, typename Args, typename K>
-static bool try_tile(K kernel, int nt, long nblk, int cus, bool last_solo, hipStream_t s, const Args& a) {
-  if (!fits(kernel, nt, nblk, cus) && !last_solo) return false;
-  klaunch(kernel, nblk, nt, 0, s, a);
-  return true;
-}
-
-template <int H, int G>
-static int launch_fwd(const LstmFwdArgs& a, int force_bs, int cus, hipStream_t s) {
-  constexpr int NT = LstmNT<H, G>::value;
-  const long groups1 = a.B;
-  if constexpr (H == 256 && G == 8) {
-    if (g_mx && force_bs <= 0 && (!a.stamps || g_mx == 2)) {
-      const int bs = valu_bs(lstm_fwd_kernel<H, G, 1>, lstm_fwd_kernel<H, G, 2>, lstm_fwd_kernel<H, G, 4>,
-                             lstm_fwd_kernel<H, G, 8>, lstm_fwd_kernel<H, G, 16>, NT, a.nprob, a.B, G, cus);
-      if (g_mx == 2 || bs == 0 || bs >= g_mx_min_bs) {
-        const int r = launch_fwd_mx(a, cus, s);
-        if (r != 0) return r < 0 ? 1 : 0;
-      }
-    }
-  }
-  constexpr int BMAX = tile_ok<H, G, 16>() ? 16 : tile_ok<H, G, 8>() ? 8 : tile_ok<H, G, 4>() ? 4 : 2;
-  for (int bs = 1; bs <= BMAX; bs *= 2) {
-    if (force_bs > 0 && bs != force_bs) continue;
-    long nblk = (long)a.nprob * ((groups1 + bs - 1) / bs) * G;
-    const bool last = G == 1 && (bs == BMAX || bs == force_bs);
-    bool ok = false;
-    switch (bs) {
-      case 1: ok = try_tile<1>(lstm_fwd_kernel<H, G, 1>, NT, nblk, cus, last, s, a); break;
-      case 2: ok = try_tile<2>(lstm_fwd_kernel<H, G, 2>, NT, nblk, cus, last, s, a); break;
-      case 4: if constexpr (tile_ok<H, G, 4>()) ok = try_tile<4>(lstm_fwd_kernel<H, G, 4>, NT, nblk, cus, last, s, a); break;
-      case 8: if constexpr (tile_ok<H, G, 8>()) ok = try_tile<8>(lstm_fwd_kernel<H, G, 8>, NT, nblk, cus, last, s, a); break;
-      default: if constexpr (tile_ok<H, G, 16>()) ok = try_tile<16>(lstm_fwd_kernel<H, G, 16>, NT, nblk, cus, last, s, a); break;
-    }
-    if (ok) return check_launch("lstm_fwd_kernel");
-  }
-  set_error("lstm fwd: persistent grid does not fit the GPU (nprob=%d B=%d H=%d force_bs=%d)", a.nprob, a.B, H,
-            force_bs);
-  return 4;
-}
+static int g_mx_min_bs_bwd = env_int("MRG_LSTM_MX_MIN_BS_BWD", 0);
 
 static int g_bwd_blocks_per_cu = 0;  // cap on resident workgroups per CU (mrg_lstm_set_blocks_per_cu)
 
+// kernel families of launch_tiles (lstm_common.h)
+template <int H, int G, bool BWD>
+struct LstmTiles {
+  static constexpr int NT = LstmNT<H, G>::value, BCAP = 16;
+  static constexpr const char* name = BWD ? "lstm_bwd_kernel" : "lstm_fwd_kernel";
+  template <int BS>
+  static constexpr bool ok() { return tile_ok<H, G, BS>(); }
+  template <int BS>
+  static auto kernel() {
+    if constexpr (BWD) return lstm_bwd_kernel<H, G, BS>;
+    else return lstm_fwd_kernel<H, G, BS>;
+  }
+  template <typename Args>
+  static int no_fit(const Args& a, int force_bs, int) {
+    set_error("lstm %s: persistent grid does not fit the GPU (nprob=%d B=%d H=%d force_bs=%d)", BWD ? "bwd" : "fwd",
+              a.nprob, a.B, H, force_bs);
+    return 4;
+  }
+};
 template <int H, int G>
-static int launch_bwd(const LstmBwdArgs& a, int force_bs, int cus, hipStream_t s) {
-  constexpr int NT = LstmNT<H, G>::value;
-  // (the MFMA form runs one workgroup per CU, within a cap of one: mrg_lstm_set_blocks_per_cu)
-  if constexpr (H == 256 && G == 8) {
-    if (g_mx && force_bs <= 0 && (!a.stamps || g_mx == 2) && g_bwd_blocks_per_cu <= 1) {
-      const int bs = valu_bs(lstm_bwd_kernel<H, G, 1>, lstm_bwd_kernel<H, G, 2>, lstm_bwd_kernel<H, G, 4>,
-                             lstm_bwd_kernel<H, G, 8>, lstm_bwd_kernel<H, G, 16>, NT, a.nprob, a.B, G, cus);
-      if (g_mx == 2 || bs == 0 || bs >= (g_mx_min_bs_bwd > 0 ? g_mx_min_bs_bwd : g_mx_min_bs)) {
-        const int r = launch_bwd_mx(a, cus, s);
-        if (r != 0) return r < 0 ? 1 : 0;
-      }
-    }
-  }
-  constexpr int BMAX = tile_ok<H, G, 16>() ? 16 : tile_ok<H, G, 8>() ? 8 : tile_ok<H, G, 4>() ? 4 : 2;
-  for (int bs = 1; bs <= BMAX; bs *= 2) {
-    if (force_bs > 0 && bs != force_bs) continue;
-    long nblk = (long)a.nprob * ((a.B + bs - 1) / bs) * G;
-    const bool last = G == 1 && (bs == BMAX || bs == force_bs);
-    if (force_bs <= 0 && g_bwd_blocks_per_cu > 0 && bs < BMAX && nblk > (long)g_bwd_blocks_per_cu * cus) continue;
-    bool ok = false;
-    switch (bs) {
-      case 1: ok = try_tile<1>(lstm_bwd_kernel<H, G, 1>, NT, nblk, cus, last, s, a); break;
-      case 2: ok = try_tile<2>(lstm_bwd_kernel<H, G, 2>, NT, nblk, cus, last, s, a); break;
-      case 4: if constexpr (tile_ok<H, G, 4>()) ok = try_tile<4>(lstm_bwd_kernel<H, G, 4>, NT, nblk, cus, last, s, a); break;
-      case 8: if constexpr (tile_ok<H, G, 8>()) ok = try_tile<8>(lstm_bwd_kernel<H, G, 8>, NT, nblk, cus, last, s, a); break;
-      default: if constexpr (tile_ok<H, G, 16>()) ok = try_tile<16>(lstm_bwd_kernel<H, G, 16>, NT, nblk, cus, last, s, a); break;
-    }
-    if (ok) return check_launch("lstm_bwd_kernel");
-  }
-  set_error("lstm bwd: persistent grid does not fit the GPU (nprob=%d B=%d H=%d force_bs=%d)", a.nprob, a.B, H,
-            force_bs);
-  return 4;
+using LstmFwdTiles = LstmTiles<H, G, false>;
+template <int H, int G>
+using LstmBwdTiles = LstmTiles<H, G, true>;
+
+// Whether the MFMA form takes a launch of the (H = 256, G = 8) family F: never a forced tile, stamped
+// launches only in mode 2; in mode 1 when the VALU walk (dry) finds no tile or one of at least min_bs.
+template <typename F, typename Args>
+static bool wants_mx(const Args& a, int force_bs, int cus, int min_bs, hipStream_t s) {
+  if (!g_mx || force_bs > 0 || (a.stamps && g_mx != 2)) return false;
+  const int bs = launch_tiles<F>(a, a.nprob, a.B, 8, cus, 0, s, NoSkip{}, true);
+  return g_mx == 2 || bs == 0 || bs >= min_bs;
 }
 
-static int g_group256 = [] {  // members per group at H = 256 (4, 8 or 16), mrg_lstm_config / MRG_LSTM_GROUP256
-  const char* e = getenv("MRG_LSTM_GROUP256");
-  const int g = e ? atoi(e) : 8;
+// members per group at H = 256 (4, 8 or 16), mrg_lstm_config / MRG_LSTM_GROUP256
+static int g_group256 = [] {
+  const int g = env_int("MRG_LSTM_GROUP256", 8);
   return (g == 4 || g == 16) ? g : 8;
 }();
 
 // solo groups (G = 1) at H <= 128: MRG_LSTM_SOLO=0 / mrg_lstm_set_solo(0) restores the multi-member groups
-static int g_solo = [] {
-  const char* e = getenv("MRG_LSTM_SOLO");
-  return (e && atoi(e) == 0) ? 0 : 1;
-}();
+static int g_solo = env_int("MRG_LSTM_SOLO", 1) != 0;
 
 // members per group without solo groups (the hand-off ring is sized for these)
 // forward-only ring size at H = 256 (MRG_LSTM_GROUP256_FWD = 4 / 8 / 16; unset: the shared setting)
 static int g_fwd_group256 = [] {
-  const char* e = getenv("MRG_LSTM_GROUP256_FWD");
-  const int g = e ? atoi(e) : 0;
+  const int g = env_int("MRG_LSTM_GROUP256_FWD", 0);
   return (g == 4 || g == 8 || g == 16) ? g : 0;
 }();
 
@@ -600,10 +533,8 @@ using namespace mrg;
 
 static unsigned long long* g_stamps = nullptr;
 static int g_inject = 0;
-static int g_local = [] {  // granule stores at workgroup scope (see put_granule); MRG_LSTM_LOCAL=0 disables
-  const char* e = getenv("MRG_LSTM_LOCAL");
-  return (e && atoi(e) == 0) ? 0 : 1;
-}();
+// granule stores at workgroup scope (see put_granule); MRG_LSTM_LOCAL=0 disables
+static int g_local = env_int("MRG_LSTM_LOCAL", 1) != 0;
 
 // Granule store scope of the recurrences' hand-offs: 1 = workgroup scope (line kept in L2), 0 = agent.
 MRG_API int mrg_lstm_set_local_handoff(int on) {
@@ -703,14 +634,17 @@ MRG_API int mrg_lstm_fwd(int nprob, int B, int T, int H,
     MRG_REQUIRE(((uintptr_t)p.w_hh & 15) == 0, "mrg_lstm_fwd: w_hh must be 16-byte aligned");
   }
   if (cus <= 0) cus = device_cus();
+  if (H == 256 && G == 8 && wants_mx<LstmFwdTiles<256, 8>>(a, force_bs, cus, g_mx_min_bs, stream)) {
+    const int r = launch_fwd_mx(a, cus, stream);
+    if (r != 0) return r < 0 ? 1 : 0;
+  }
+  auto go = [&](auto f) { return launch_tiles<decltype(f)>(a, nprob, B, G, cus, force_bs, stream); };
   switch (H) {
-    case 256: return G == 8   ? launch_fwd<256, 8>(a, force_bs, cus, stream)
-                     : G == 4 ? launch_fwd<256, 4>(a, force_bs, cus, stream)
-                              : launch_fwd<256, 16>(a, force_bs, cus, stream);
-    case 128: return G == 1 ? launch_fwd<128, 1>(a, force_bs, cus, stream) : launch_fwd<128, 8>(a, force_bs, cus, stream);
-    case 64: return G == 1 ? launch_fwd<64, 1>(a, force_bs, cus, stream) : launch_fwd<64, 4>(a, force_bs, cus, stream);
-    case 32: return G == 1 ? launch_fwd<32, 1>(a, force_bs, cus, stream) : launch_fwd<32, 2>(a, force_bs, cus, stream);
-    case 16: return launch_fwd<16, 1>(a, force_bs, cus, stream);
+    case 256: return G == 8 ? go(LstmFwdTiles<256, 8>{}) : G == 4 ? go(LstmFwdTiles<256, 4>{}) : go(LstmFwdTiles<256, 16>{});
+    case 128: return G == 1 ? go(LstmFwdTiles<128, 1>{}) : go(LstmFwdTiles<128, 8>{});
+    case 64: return G == 1 ? go(LstmFwdTiles<64, 1>{}) : go(LstmFwdTiles<64, 4>{});
+    case 32: return G == 1 ? go(LstmFwdTiles<32, 1>{}) : go(LstmFwdTiles<32, 2>{});
+    case 16: return go(LstmFwdTiles<16, 1>{});
   }
   return 2;
 }
@@ -746,14 +680,22 @@ MRG_API int mrg_lstm_bwd(int nprob, int B, int T, int H,
     p.dG_bs = L ? L[5] : (long)T * 4 * H; p.dG_ts = L ? L[6] : 4 * H;
   }
   if (cus <= 0) cus = device_cus();
+  // (the MFMA form runs one workgroup per CU, within a cap of one: mrg_lstm_set_blocks_per_cu)
+  if (H == 256 && G == 8 && g_bwd_blocks_per_cu <= 1 &&
+      wants_mx<LstmBwdTiles<256, 8>>(a, force_bs, cus, g_mx_min_bs_bwd > 0 ? g_mx_min_bs_bwd : g_mx_min_bs, stream)) {
+    const int r = launch_bwd_mx(a, cus, stream);
+    if (r != 0) return r < 0 ? 1 : 0;
+  }
+  // under a cap on workgroups per CU, un-forced launches pass over the tiles (but the largest) that exceed it
+  const long cap = g_bwd_blocks_per_cu;
+  auto over_cap = [=](int bs, int bmax, long nblk) { return force_bs <= 0 && cap > 0 && bs < bmax && nblk > cap * cus; };
+  auto go = [&](auto f) { return launch_tiles<decltype(f)>(a, nprob, B, G, cus, force_bs, stream, over_cap); };
   switch (H) {
-    case 256: return G == 8   ? launch_bwd<256, 8>(a, force_bs, cus, stream)
-                     : G == 4 ? launch_bwd<256, 4>(a, force_bs, cus, stream)
-                              : launch_bwd<256, 16>(a, force_bs, cus, stream);
-    case 128: return G == 1 ? launch_bwd<128, 1>(a, force_bs, cus, stream) : launch_bwd<128, 8>(a, force_bs, cus, stream);
-    case 64: return G == 1 ? launch_bwd<64, 1>(a, force_bs, cus, stream) : launch_bwd<64, 4>(a, force_bs, cus, stream);
-    case 32: return G == 1 ? launch_bwd<32, 1>(a, force_bs, cus, stream) : launch_bwd<32, 2>(a, force_bs, cus, stream);
-    case 16: return launch_bwd<16, 1>(a, force_bs, cus, stream);
+    case 256: return G == 8 ? go(LstmBwdTiles<256, 8>{}) : G == 4 ? go(LstmBwdTiles<256, 4>{}) : go(LstmBwdTiles<256, 16>{});
+    case 128: return G == 1 ? go(LstmBwdTiles<128, 1>{}) : go(LstmBwdTiles<128, 8>{});
+    case 64: return G == 1 ? go(LstmBwdTiles<64, 1>{}) : go(LstmBwdTiles<64, 4>{});
+    case 32: return G == 1 ? go(LstmBwdTiles<32, 1>{}) : go(LstmBwdTiles<32, 2>{});
+    case 16: return go(LstmBwdTiles<16, 1>{});
   }
   return 2;
 }

@@ -1,6 +1,7 @@
-// Shared pieces of the persistent LSTM recurrences (lstm.hip: VALU GEMV form; lstm_mx.hip: MFMA
-// form for batch tiles of 16 rows): problem / argument blocks, the {tag, value} granule hand-off,
-// the block -> (problem, group, member) map and the co-residency check.
+// Shared pieces of the persistent recurrences (lstm.hip, gru_rec.hip: VALU GEMV form; lstm_mx.hip: MFMA
+// form of the LSTM for batch tiles of 16 rows): the LSTM's problem / argument blocks, the {tag, value}
+// granule hand-off, the block -> (problem, group, member) map, the co-residency check and the batch-tile
+// launcher (launch_tiles) that all four VALU kernels go through.
 #pragma once
 #include "mrg_common.h"
 
@@ -284,6 +285,58 @@ static bool fits(K kernel, int nt, long nblk, int cus) {
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return 0;
   return n;
+}
+
+// ---- The batch-tile launcher of the VALU recurrences.  A kernel family F (one per kernel and (H, G)) has
+//   NT, BCAP            threads per workgroup; largest batch tile the family is built for (16 or 8)
+//   ok<BS>()            whether tile BS is instantiated,   kernel<BS>()   its kernel
+//   name                for check_launch
+//   no_fit(a, force, bmax)   sets the error of a walk that launched nothing and returns its code
+struct NoSkip {
+  bool operator()(int, int, long) const { return false; }
+};
+
+// one candidate tile: true when its grid fits (or always_fits), launched unless dry
+template <typename F, int BS, typename Args>
+static bool take_tile(const Args& a, long nblk, int cus, bool always_fits, bool dry, hipStream_t s) {
+  if constexpr (BS <= F::BCAP && F::template ok<BS>()) {
+    auto kernel = F::template kernel<BS>();
+    if (!fits(kernel, F::NT, nblk, cus) && !always_fits) return false;
+    if (!dry) klaunch(kernel, nblk, F::NT, 0, s, a);
+    return true;
+  }
+  return false;
+}
+
+// Walks the batch tiles 1, 2, 4, ... of F and launches the first whose grid of nprob * ceil(B / bs) * G
+// workgroups fits the GPU at once; force > 0 admits that tile only (a forced ring tile must still fit).
+// A solo group's (G = 1) last candidate always launches: its workgroups never wait on each other, so a
+// grid larger than the GPU still completes.  skip(bs, bmax, nblk) passes a candidate over.
+// dry: nothing is launched and no candidate is taken for its position; returns the tile the grid first
+// fits (0 = none).  Otherwise returns the entry point's code.
+template <typename F, typename Args, typename Skip = NoSkip>
+static int launch_tiles(const Args& a, int nprob, int B, int G, int cus, int force, hipStream_t s, Skip skip = {},
+                        bool dry = false) {
+  constexpr int BMAX = (F::BCAP >= 16 && F::template ok<16>()) ? 16
+                       : F::template ok<8>()                   ? 8
+                       : F::template ok<4>()                   ? 4
+                                                               : 2;
+  for (int bs = 1; bs <= BMAX; bs *= 2) {
+    if (force > 0 && bs != force) continue;
+    const long nblk = (long)nprob * ((B + bs - 1) / bs) * G;
+    const bool last = !dry && G == 1 && (bs == BMAX || bs == force);
+    if (skip(bs, BMAX, nblk)) continue;
+    bool ok = false;
+    switch (bs) {
+      case 1: ok = take_tile<F, 1>(a, nblk, cus, last, dry, s); break;
+      case 2: ok = take_tile<F, 2>(a, nblk, cus, last, dry, s); break;
+      case 4: ok = take_tile<F, 4>(a, nblk, cus, last, dry, s); break;
+      case 8: ok = take_tile<F, 8>(a, nblk, cus, last, dry, s); break;
+      default: ok = take_tile<F, 16>(a, nblk, cus, last, dry, s); break;
+    }
+    if (ok) return dry ? bs : check_launch(F::name);
+  }
+  return dry ? 0 : F::no_fit(a, force, BMAX);
 }
 
 }  // namespace mrg

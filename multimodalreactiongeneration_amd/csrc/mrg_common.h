@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cmath>
+#include <cstdlib>
 
 #include <hip/hip_ext.h>
 
@@ -49,6 +50,12 @@ inline int check_launch(const char* what) {
     return 1;
   }
   return 0;
+}
+
+// An int knob from the environment; dflt when the variable is unset.  Each site validates the value itself.
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
 }
 
 #define MRG_REQUIRE(cond, ...)            \

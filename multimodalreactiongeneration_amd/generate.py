@@ -75,9 +75,9 @@ def _few_row_gemm(*args, **kw):
 # per 8 CUs.  Each is one persistent launch whose whole grid must be resident, one workgroup per CU, so N
 # sequences go through in chunks of that many times CUs / 8.
 _RECURRENCE = {
-    # at H = 256 eight workgroups serve at most 16 sequences (lstm.hip launch_fwd, lstm_mx.hip): 512 on 256 CUs
+    # at H = 256 eight workgroups serve at most 16 sequences (lstm_common.h launch_tiles, lstm_mx.hip): 512 on 256 CUs
     "lstm": (Fn.lstm_layer, 16),
-    # the GRU's launch has the same residency rule and no fallback (gru_rec.hip gru_launch_fwd returns an
+    # the GRU's launch has the same residency rule and no fallback (gru_rec.hip: launch_tiles returns an
     # error when no batch tile fits): at H = 256 a ring of 4 or 8 workgroups (mrg_gru_config) serves at
     # most 8 sequences, so with the larger ring 256 on 256 CUs
     "gru": (Fn.gru_layer, 8),
