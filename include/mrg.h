@@ -521,6 +521,13 @@ int mrg_fill_zero(void* p, long bytes, hipStream_t stream);
 int mrg_activation_fwd(long n, int kind, const float* x, float* y, hipStream_t stream);
 int mrg_activation_bwd(long n, int kind, const float* dy, const float* saved, float* dx,
                        hipStream_t stream);
+/* y = a + b over n floats (any alignment; 16-B accesses when all three pointers are aligned, the
+ * scalar form otherwise and on the tail past n & ~3); y may be a.  The residual connection without a
+ * LayerNorm (ResidualConnection(use_layer_norm=False), residual_connection.py:29-37) where no GEMM
+ * feeds the sum: around a recurrence and in the one-key attention form.  Where a GEMM does, the add
+ * is that GEMM's epilogue 3 and this entry point is not called.  The backward is the identity to
+ * both operands and has no kernel.                                                                */
+int mrg_residual_add(long n, const float* a, const float* b, float* y, hipStream_t stream);
 /* dst [n1][n0][E] = src [n0][n1][E] (beta = 1: dst +=): the batch-major [B, T, E] <-> time-major
  * [T, B, E] activations and gradients at the metaformer blocks' wavefront boundaries
  * (multi_modal_metaformer.py:501-502 feeds block outputs forward batch-major).  E % 4 == 0.     */

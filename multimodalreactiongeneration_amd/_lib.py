@@ -144,6 +144,7 @@ SIGNATURES = {
     "mrg_fill_zero": (c_int, [P, c_long, P]),
     "mrg_activation_fwd": (c_int, [c_long, c_int, P, P, P]),
     "mrg_activation_bwd": (c_int, [c_long, c_int, P, P, P, P]),
+    "mrg_residual_add": (c_int, [c_long, P, P, P, P]),
     "mrg_probe_start": (c_int, [c_int]),
     "mrg_probe_tag": (c_int, [c_int]),
     "mrg_probe_stop": (c_int, [ctypes.POINTER(ctypes.c_float), PI, c_int]),

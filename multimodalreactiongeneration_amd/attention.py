@@ -150,8 +150,11 @@ class _MHAFn(Function):
     def forward(ctx, spec, q_in, kv_in, in_w, in_b, out_w, out_b, qpad, kpad, gamma=None, beta=None):
         # eps not None: return LN(attn + q) (ResidualConnection(MHAMixer)); p > 0: dropout on the
         # attention probabilities with one draw, the key saved for the backward
+        # addq: return attn + q (the residual without a LayerNorm), q added by the output projection's
+        # epilogue 3
         heads, causal, eps, *rest = spec
         p = rest[0] if rest else 0.0
+        addq = bool(rest[1]) if len(rest) > 1 else False
         _lib.require_device(q_in)
         dev = q_in.device
         B, Tq, E = q_in.shape
@@ -178,7 +181,8 @@ class _MHAFn(Function):
                 rc = lib.mrg_attention_fwd(*args, _stream())
         _lib.check(rc, "attention fwd")
         out = torch.empty(B, Tq, E, device=dev, dtype=torch.float32)
-        _fwd_gemm(B * Tq, E, E, _ptr(O), E, out_w, _ptr(out), E, bias=_ptr(out_b), device=dev)
+        kw = dict(epi=3, aux=_ptr(q2), ldaux=E) if addq else {}
+        _fwd_gemm(B * Tq, E, E, _ptr(O), E, out_w, _ptr(out), E, bias=_ptr(out_b), device=dev, **kw)
         # dO = dout W_out runs in every backward (the in_proj weight gradient needs dO even when
         # neither input does), so out_w is noted unconditionally (a stale copy is never reused)
         _wt_note(out_w, B * Tq)
@@ -192,6 +196,7 @@ class _MHAFn(Function):
             extra = [out, gamma, beta, mean, rstd]
         ctx.save_for_backward(q2, kv2, Q, KV, O, lse, in_w, in_b, out_w, out_b, qpad, kpad, *extra)
         ctx.spec = (heads, causal, scale, eps is not None)
+        ctx.addq = addq
         ctx.drop = drop
         return res
 
@@ -214,6 +219,8 @@ class _MHAFn(Function):
             do2 = g.view(B, Tq, E)
         else:
             do2 = dout.contiguous()
+            if ctx.addq:   # attn + q: dq = dQ W_q + dout, by the same epilogue
+                g = do2.view(B * Tq, E)
         dO = torch.empty(B, Tq, E, device=dev, dtype=torch.float32)
         _dx_gemm(B * Tq, E, E, _ptr(do2), E, out_w, _ptr(dO), E, device=dev)
         _wgrad(_ptr(do2), E, _ptr(O), E, B * Tq, E, E, _gbuf(out_w), dev, gb=_gbuf(out_b), keep=(do2, O))
@@ -258,6 +265,8 @@ class _MHAOneKeyFn(Function):
     @staticmethod
     @_keeps_precision
     def forward(ctx, eps, q_in, kv_in, in_w, in_b, out_w, out_b, qpad, kpad, gamma=None, beta=None):
+        addq = eps == "add"   # attn + q without a LayerNorm: q added by the output projection's epilogue 3
+        eps = None if addq else eps
         _lib.require_device(q_in)
         dev = q_in.device
         B, _, E = q_in.shape
@@ -271,7 +280,8 @@ class _MHAOneKeyFn(Function):
             hide = (qpad.reshape(B, 1) & kpad.reshape(B, 1)).bool()
             O = torch.where(hide, torch.full_like(V, float("nan")), V)
         out = torch.empty(B, E, device=dev, dtype=torch.float32)
-        gemm(B, E, E, _ptr(O), 0, E, _ptr(out_w), 1, E, _ptr(out), E, bias=_ptr(out_b), device=dev)
+        kw = dict(epi=3, aux=_ptr(q2), ldaux=E) if addq else {}
+        gemm(B, E, E, _ptr(O), 0, E, _ptr(out_w), 1, E, _ptr(out), E, bias=_ptr(out_b), device=dev, **kw)
         res = out
         extra = []
         if eps is not None:
@@ -281,6 +291,7 @@ class _MHAOneKeyFn(Function):
         ctx.save_for_backward(q2, kv2, O, in_w, in_b, out_w, out_b, *extra)
         ctx.hide = hide
         ctx.resln = eps is not None
+        ctx.addq = addq
         return res.view(B, 1, E)
 
     @staticmethod
@@ -297,6 +308,8 @@ class _MHAOneKeyFn(Function):
             do2 = g
         else:
             do2 = dout.reshape(B, E).contiguous()
+            if ctx.addq:
+                g = do2
         dO = torch.empty(B, E, device=dev, dtype=torch.float32)
         gemm(B, E, E, _ptr(do2), 0, E, _ptr(out_w), 0, E, _ptr(dO), E, device=dev)
         _wgrad(_ptr(do2), E, _ptr(O), E, B, E, E, _gbuf(out_w), dev, gb=_gbuf(out_b), keep=(do2, O))
@@ -318,15 +331,17 @@ def _one_key(q, kv):
 
 
 def _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
-         eps=None, ln=()):
-    """The attention Function for these shapes; eps not None: LN(. + q) with ln = (gamma, beta)."""
+         eps=None, ln=(), addq=False):
+    """The attention Function for these shapes; eps not None: LN(. + q) with ln = (gamma, beta); addq:
+    . + q without a LayerNorm."""
     if in_proj_weight.shape[0] != 3 * q.shape[-1]:
         raise ValueError("in_proj_weight must be [3E, E]")
     p = float(dropout_p)
     _drop_consts(p)
     if p == 0.0 and _one_key(q, kv):   # with dropout the single probability 1 is still dropped: _MHAFn
-        return _MHAOneKeyFn.apply(eps, q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, qpad, kpad, *ln)
-    return _MHAFn.apply((heads, bool(causal), eps, p), q, kv, in_proj_weight, in_proj_bias, out_weight,
+        return _MHAOneKeyFn.apply("add" if addq else eps, q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias,
+                                  qpad, kpad, *ln)
+    return _MHAFn.apply((heads, bool(causal), eps, p, bool(addq)), q, kv, in_proj_weight, in_proj_bias, out_weight,
                         out_bias, qpad, kpad, *ln)
 
 
@@ -343,3 +358,13 @@ def mha_residual_layernorm(q, kv, in_proj_weight, in_proj_bias, out_weight, out_
     projection's input-gradient GEMM takes the residual gradient in its epilogue."""
     return _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
                 float(eps), (gamma, beta))
+
+
+def mha_residual(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal=False,
+                 qpad=None, kpad=None, dropout_p=0.0):
+    """MHA(q, kv, kv) + q: ResidualConnection(MHAMixer) without a LayerNorm.  q is added by the output
+    projection's GEMM (epilogue 3) in both forms of mha, and the gradient of the sum by the query
+    projection's input-gradient GEMM (the one-key form has no query projection: there dq is the
+    gradient itself)."""
+    return _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
+                addq=True)

@@ -89,12 +89,49 @@ def residual_layernorm(y, x, gamma, beta, eps=1e-5):
     return _ResLNFn.apply(y, x, gamma, beta, eps)
 
 
+# ------------------------------------------------------------------ residual without LayerNorm
+def _residual_add_launch(a, b, out):
+    """out = a + b over contiguous fp32 tensors of one size (out may be a)."""
+    _lib.check(_lib.load().mrg_residual_add(a.numel(), _ptr(a), _ptr(b), _ptr(out), _stream()), "residual add")
+    return out
+
+
+class _ResAddFn(Function):
+    @staticmethod
+    @_keeps_precision
+    def forward(ctx, y, x):
+        yc, xc = y.contiguous(), x.contiguous()
+        return _residual_add_launch(yc, xc, torch.empty_like(yc))
+
+    @staticmethod
+    @_keeps_precision
+    def backward(ctx, dy):
+        return dy, dy
+
+
+def residual_add(y, x, inplace=False):
+    """y + x — ResidualConnection without a LayerNorm (residual_connection.py:29-37) where no GEMM
+    epilogue carries the add; the gradient goes to both operands as it is.  inplace: write the sum
+    over y when nothing can read y again, which holds only outside autograd (a recurrence keeps its
+    output for the backward's recurrent weight gradient); under autograd a new tensor is returned."""
+    _lib.require_device(y)
+    if y.shape != x.shape:
+        raise ValueError(f"residual_add: shapes differ, {tuple(y.shape)} and {tuple(x.shape)}")
+    if y.dtype != torch.float32 or x.dtype != torch.float32:
+        raise ValueError("residual_add: float32 tensors required")
+    if inplace and y.is_contiguous() and not (torch.is_grad_enabled() and (y.requires_grad or x.requires_grad)):
+        return _residual_add_launch(y, x.contiguous(), y)
+    return _ResAddFn.apply(y, x)
+
+
 # ------------------------------------------------------------------ Linear, alone and under LN(. + x)
-def _linear_fwd(ctx, x2, w, b):
-    """x2 w^T + b; w is noted for the backward's input-gradient product."""
+def _linear_fwd(ctx, x2, w, b, residual=None):
+    """x2 w^T + b (+ residual [M, N] by the GEMM's epilogue 3); w is noted for the backward's
+    input-gradient product."""
     M, (N, In) = x2.shape[0], w.shape
     y = torch.empty(M, N, device=x2.device, dtype=torch.float32)
-    _fwd_gemm(M, N, In, _ptr(x2), In, w, _ptr(y), N, bias=_ptr(b), device=x2.device)
+    kw = {} if residual is None else dict(epi=3, aux=_ptr(residual), ldaux=N)
+    _fwd_gemm(M, N, In, _ptr(x2), In, w, _ptr(y), N, bias=_ptr(b), device=x2.device, **kw)
     _wt_note(w, M, ctx.needs_input_grad[0])
     return y
 
@@ -152,6 +189,71 @@ def linear_residual_layernorm(x, weight, bias, gamma, beta, eps=1e-5):
     return _LinResLNFn.apply(x, weight, bias, gamma, beta, eps)
 
 
+def _square(w, what):
+    if w.shape[0] != w.shape[1]:
+        raise ValueError(f"{what}: the residual needs equal input and output sizes, got weight {tuple(w.shape)}")
+
+
+class _LinResFn(Function):
+    """x W^T + b + x: FeedForward(nonlinearity none, residual, no LN) (mixer_block.py:63-83).  The
+    forward GEMM adds x and the input-gradient GEMM adds dy, both by epilogue 3: no add launch and
+    no [rows, E] intermediate in either direction."""
+
+    @staticmethod
+    @_keeps_precision
+    def forward(ctx, x, w, b):
+        x2 = _rows(x, w.shape[1])
+        y = _linear_fwd(ctx, x2, w, b, residual=x2)
+        ctx.save_for_backward(x2, w, b)
+        ctx.xshape = x.shape
+        return y.view(x.shape)
+
+    @staticmethod
+    @_keeps_precision
+    def backward(ctx, dy):
+        x2, w, b = ctx.saved_tensors
+        g = dy.reshape(x2.shape).contiguous()
+        return _linear_bwd(ctx, g, x2, w, b, residual=g), None, None
+
+
+def linear_residual(x, weight, bias=None):
+    _square(weight, "linear_residual")
+    return _LinResFn.apply(x, weight, bias)
+
+
+class _LinAddFn(Function):
+    """h W^T + b + r with r in the output's shape: the last Linear of a module under a residual
+    connection without LayerNorm whose skip operand r is not that Linear's input (the mixing Linear
+    of LSTMModule, the projection of MultiModalAttentionBlockSequential).  r is added by the forward
+    GEMM's epilogue 3; its gradient is dy as it is."""
+
+    @staticmethod
+    @_keeps_precision
+    def forward(ctx, h, w, b, r):
+        h2 = _rows(h, w.shape[1])
+        r2 = r.reshape(-1, w.shape[0]).contiguous()
+        y = _linear_fwd(ctx, h2, w, b, residual=r2)
+        ctx.save_for_backward(h2, w, b)
+        ctx.xshape = h.shape
+        return y.view(r.shape)
+
+    @staticmethod
+    @_keeps_precision
+    def backward(ctx, dy):
+        h2, w, b = ctx.saved_tensors
+        g = dy.reshape(-1, w.shape[0]).contiguous()
+        return _linear_bwd(ctx, g, h2, w, b), None, None, (dy if ctx.needs_input_grad[3] else None)
+
+
+def linear_add(h, weight, bias, r):
+    """linear(h) + r, r [..., out]; the add is the GEMM's epilogue."""
+    if tuple(r.shape) != (*h.shape[:-1], weight.shape[0]):
+        raise ValueError(f"linear_add: r {tuple(r.shape)} is not the output's shape "
+                         f"{(*h.shape[:-1], weight.shape[0])}")
+    _lib.require_device(r)
+    return _LinAddFn.apply(h, weight, bias, r)
+
+
 # ------------------------------------------------------------------ FFN (Linear -> act -> Linear)
 # Test hook (None in the product path): when a dict, every FFN forward stores the ReLU's side per
 # element, {w1.data_ptr(): bool [..., Hb] (pre-activation > 0)}, so a test can evaluate the float64
@@ -186,16 +288,17 @@ def _act_fwd_gemm(M, Hb, In, x2, w1, b1, fe, dev):
     return h, pre
 
 
-def _ffn_fwd(ctx, x, w1, b1, w2, b2, act):
-    """(x2, h, pre, z): z = act(x2 w1^T + b1) w2^T + b2 over x's rows.  Only w1 is noted: the dh
-    product reads w2 through gemm directly."""
+def _ffn_fwd(ctx, x, w1, b1, w2, b2, act, residual=False):
+    """(x2, h, pre, z): z = act(x2 w1^T + b1) w2^T + b2 over x's rows (residual: + x2, by the second
+    GEMM's epilogue 3).  Only w1 is noted: the dh product reads w2 through gemm directly."""
     fe, ctx.be, _ = _act_codes(act)
     (Hb, In), N = w1.shape, w2.shape[0]
     x2 = _rows(x, In)
     M, dev = x2.shape[0], x.device
     h, pre = _act_fwd_gemm(M, Hb, In, x2, w1, b1, fe, dev)
     z = torch.empty(M, N, device=dev, dtype=torch.float32)
-    _fwd_gemm(M, N, Hb, _ptr(h), Hb, w2, _ptr(z), N, bias=_ptr(b2), device=dev)
+    kw = dict(epi=3, aux=_ptr(x2), ldaux=In) if residual else {}
+    _fwd_gemm(M, N, Hb, _ptr(h), Hb, w2, _ptr(z), N, bias=_ptr(b2), device=dev, **kw)
     _wt_note(w1, M, ctx.needs_input_grad[0])
     if act == "relu":
         _tap_relu(w1, h, x.shape[:-1])
@@ -259,6 +362,34 @@ class _FFNResLNFn(Function):
 
 def ffn_residual_layernorm(x, w1, b1, w2, b2, gamma, beta, eps=1e-5, act="relu"):
     return _FFNResLNFn.apply(x, w1, b1, w2, b2, gamma, beta, eps, act)
+
+
+class _FFNResFn(Function):
+    """W2 act(W1 x + b1) + b2 + x: the residual FeedForward without a LayerNorm.  x is added by the
+    second forward GEMM and dy by the input-gradient GEMM (epilogue 3 both times)."""
+
+    @staticmethod
+    @_keeps_precision
+    def forward(ctx, x, w1, b1, w2, b2, act="relu"):
+        x2, h, pre, z = _ffn_fwd(ctx, x, w1, b1, w2, b2, act, residual=True)
+        ctx.save_for_backward(x2, h, w1, b1, w2, b2, pre)
+        return z.view(x.shape)
+
+    @staticmethod
+    @_keeps_precision
+    def backward(ctx, dy):
+        x2, h, w1, b1, w2, b2, pre = ctx.saved_tensors
+        g = dy.reshape(x2.shape).contiguous()
+        return (_ffn_bwd(ctx, g, x2, h, pre, w1, b1, w2, b2, residual=g),) + (None,) * 5
+
+
+def ffn_residual(x, w1, b1, w2, b2, act="relu"):
+    """x + Linear -> act -> Linear (x), act in ACTIVATIONS; the output size must equal the input size."""
+    if w2.shape[0] != w1.shape[1]:
+        raise ValueError(f"ffn_residual: the residual needs equal input and output sizes, got {w1.shape[1]} "
+                         f"and {w2.shape[0]}")
+    _act_codes(act)
+    return _FFNResFn.apply(x, w1, b1, w2, b2, act)
 
 
 # ------------------------------------------------------------------ Linear -> act -> ... -> Linear

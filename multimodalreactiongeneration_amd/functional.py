@@ -13,6 +13,7 @@ Reference ops replaced (file:line in /root/reference):
                                                   lstm_sampler.py:16-34
   mha                 nn.MultiheadAttention       for_sequential.py:27-51, multi_modal_att.py:12-31
   residual_layernorm  ResidualConnection          residual_connection.py:20-37
+  residual_add        ... without LayerNorm       residual_connection.py:29-37
   masked_loss         training_step / lossfun     lstmformer.py:313-325,372-380
 
 This module only re-exports.  The code lives, in import order, in launch (plumbing), gemm_ops (GEMM
@@ -21,11 +22,13 @@ dispatch), then dense, recurrent, attention and losses; a switch that is rebound
 """
 from .attention import (_DropoutFn, _MHAFn, _MHAOneKeyFn, _RNG, _drop_consts, _i64, _one_key,  # noqa: F401
                         _rng_device, _rng_draw, _rng_state, attention_keep_mask, dropout, dropout_keep_mask,
-                        get_rng_state, manual_seed, mha, mha_residual_layernorm, set_rng_state, visible_pairs)
-from .dense import (ACTIVATIONS, RELU_TAP, _ActFn, _FFNFn, _FFNResLNFn, _LinearFn, _LinResLNFn,  # noqa: F401
-                    _MLPChainFn, _ResLNFn, _Sample0Fn, _act_codes, _act_fwd_gemm, _resln_bwd, _resln_fwd,
-                    _tap_relu, activation, broadcast_sample0, ffn, ffn_residual_layernorm, linear,
-                    linear_residual_layernorm, mlp_chain, residual_layernorm)
+                        get_rng_state, manual_seed, mha, mha_residual, mha_residual_layernorm, set_rng_state,
+                        visible_pairs)
+from .dense import (ACTIVATIONS, RELU_TAP, _ActFn, _FFNFn, _FFNResFn, _FFNResLNFn, _LinAddFn, _LinearFn,  # noqa: F401
+                    _LinResFn, _LinResLNFn, _MLPChainFn, _ResAddFn, _ResLNFn, _Sample0Fn, _act_codes,
+                    _act_fwd_gemm, _resln_bwd, _resln_fwd, _tap_relu, activation, broadcast_sample0, ffn,
+                    ffn_residual, ffn_residual_layernorm, linear, linear_add, linear_residual,
+                    linear_residual_layernorm, mlp_chain, residual_add, residual_layernorm)
 from .gemm_ops import (_CNT, _PL_ON, _PLANES, _WG_TARGET, _WT_CACHE, _WT_MIN_ROWS, _WT_ON, _WT_PENDING,  # noqa: F401
                        _counters, _dx_gemm, _fwd_gemm, _on_side, _plane_operand, _planes_gemm, _wgrad, _wt,
                        _wt_key, _wt_note, act_splits, colsum, gemm, invalidate_weight_planes, planes_batched,
@@ -37,8 +40,9 @@ from .launch import (_ARITH, _CALLS, _ERR, _GRAD_LISTENER, _NATIVE, _PROBE_CAP, 
 from .losses import (_LOSS_TYPES, _BcastLossFn, _LossFn, _flat_f32, _metric_buffers, _metric_ranges,  # noqa: F401
                      broadcast_masked_loss, clip_grad_norm_, clip_grad_value_, clip_grad_workspace, masked_loss,
                      padding_flags, target_metrics_update, target_metrics_update_broadcast, zero_padding)
-from .recurrent import (_GRU_PERSIST, _GRUFn, _LSTMCellFn, _LSTMFn, gru_layer, lstm_bidirectional_layer,  # noqa: F401
-                        lstm_bidirectional_layers, lstm_layer, lstm_layers_batched, lstm_residual_layernorm)
+from .recurrent import (_GRU_PERSIST, _GRUFn, _LSTMCellFn, _LSTMFn, gru_layer, gru_residual,  # noqa: F401
+                        lstm_bidirectional_layer, lstm_bidirectional_layers, lstm_bidirectional_residual,
+                        lstm_layer, lstm_layers_batched, lstm_residual, lstm_residual_layernorm)
 from .wgrad_streams import (_LAST_FORK, _SIDE_MIN_ROWS, _conflicts, _fork, _writes, allow_defer,  # noqa: F401
                             beside_recurrence, hold_scratch, on_side, reset_fork_point, set_wgrad_defer,
                             set_wgrad_stream, side as _side)

@@ -80,8 +80,21 @@ def run_sequential_ffn(seq: nn.Sequential, x):
     _unsupported(f"feed-forward {[type(m).__name__ for m in mods]}")
 
 
+def sequential_ffn_residual(seq: nn.Sequential, x):
+    """x + seq(x) for Linear or Linear -> ReLU | SiLU | Tanh -> Linear with x added by the last GEMM's
+    epilogue (functional.linear_residual / ffn_residual); None for any other stack."""
+    mods = list(seq.children())
+    if len(mods) == 1 and isinstance(mods[0], nn.Linear) and mods[0].bias is not None:
+        return Fn.linear_residual(x, mods[0].weight, mods[0].bias)
+    act = activation_name(mods[1]) if len(mods) == 3 else None
+    if act is not None and mods[0].bias is not None and mods[2].bias is not None:
+        return Fn.ffn_residual(x, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias, act)
+    return None
+
+
 class ResidualConnection(nn.Module):
-    """LN(module(x, ...) + x); tuple outputs keep their tail (residual_connection.py:20-37)."""
+    """LN(module(x, ...) + x), or module(x, ...) + x with use_layer_norm=False; tuple outputs keep
+    their tail (residual_connection.py:20-37)."""
 
     def __init__(self, module: nn.Module, use_layer_norm=True, num_nodes: int = -1, dropout=0.0):
         super().__init__()
@@ -98,7 +111,7 @@ class ResidualConnection(nn.Module):
         if self.layer_norm is not None:
             return Fn.residual_layernorm(y, x, self.layer_norm.weight, self.layer_norm.bias,
                                          self.layer_norm.eps)
-        _unsupported("residual without LayerNorm")
+        return Fn.residual_add(y, x)
 
     def forward(self, x, *args, **kwargs):
         # modules that can run LN(module(x) + x) as one fused op (the residual branch's gradient is
@@ -106,6 +119,13 @@ class ResidualConnection(nn.Module):
         fused = getattr(self.module, "fused_residual_ln", None)
         if fused is not None and self.layer_norm is not None:
             out = fused(self.layer_norm, x, *args, **kwargs)
+            if out is not None:
+                return out
+        # without a LayerNorm: modules whose last GEMM can add x in its epilogue (or that own the
+        # buffer the add may overwrite) expose fused_residual, same contract
+        fused = getattr(self.module, "fused_residual", None)
+        if fused is not None and self.layer_norm is None:
+            out = fused(x, *args, **kwargs)
             if out is not None:
                 return out
         y = self.module(x, *args, **kwargs)
@@ -149,6 +169,10 @@ class FeedForward(nn.Module):
             if act is not None:
                 return Fn.ffn_residual_layernorm(x, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias,
                                                  ln.weight, ln.bias, ln.eps, act)
+            if ln is None:
+                out = sequential_ffn_residual(ff.module, x)
+                if out is not None:
+                    return out
             return ff.combine(run_sequential_ffn(ff.module, x), x)
         return run_sequential_ffn(ff, x)
 
@@ -365,6 +389,14 @@ class LSTMModule(nn.Module):
         y = hs if self.mixer is None else self.mixer(hs)
         return y, hx
 
+    def fused_residual(self, input_tensor, hx=None):
+        """module(x) + x without a LayerNorm: with the mixing Linear the add is its GEMM's epilogue;
+        without one the ResidualConnection adds after the recurrence (None)."""
+        if self.mixer is None or self.mixer.bias is None or not isinstance(input_tensor, torch.Tensor):
+            return None
+        hs, hx = self.lstm_module(input_tensor, hx)
+        return Fn.linear_add(hs, self.mixer.weight, self.mixer.bias, input_tensor), hx
+
 
 class LSTMBlock(nn.Module):
     """Residual LSTMModule [+ residual FFN] (lstm_block.py:49-103)."""
@@ -397,7 +429,8 @@ class LSTMBlock(nn.Module):
         if self.use_feed_forward:
             ff = self.feed_forward_module
             if isinstance(ff, ResidualConnection):
-                y = ff.combine(run_sequential_ffn(ff.module, y), y)
+                out = sequential_ffn_residual(ff.module, y) if ff.layer_norm is None else None
+                y = ff.combine(run_sequential_ffn(ff.module, y), y) if out is None else out
             else:
                 y = run_sequential_ffn(ff, y)
         return y, hx
@@ -479,6 +512,11 @@ class MultiModalAttentionBlockSequential(nn.Module):
     def forward(self, modal1, modal2):
         o, _ = self.cross_modal_att(modal1, modal2, modal2)
         return self.projection(o)
+
+    def fused_residual(self, modal1, modal2):
+        """projection(att(modal1, modal2)) + modal1 with the add in the projection's GEMM epilogue."""
+        o, _ = self.cross_modal_att(modal1, modal2, modal2)
+        return Fn.linear_add(o, self.projection.weight, self.projection.bias, modal1)
 
 
 class MultimodalAttentionBlock(nn.Module):

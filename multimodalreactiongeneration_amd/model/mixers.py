@@ -75,6 +75,21 @@ class LSTMMixer(Mixer):
         u, hT, cT = Fn.lstm_residual_layernorm(x, *m.direction_params(0), ln.weight, ln.bias, ln.eps)
         return u, (hT.unsqueeze(0), cT.unsqueeze(0))
 
+    def fused_residual(self, x, hn=None):
+        """LSTM(x) + x for a one-layer LSTM (either direction count): the add runs over the layer
+        output where that is free (functional.lstm_residual).  The state is returned as nn.LSTM's."""
+        m = self.mixer
+        if not isinstance(x, torch.Tensor) or m.num_layers != 1:
+            return None
+        h0, c0 = (None, None) if hn is None else hn
+        if m.bidirectional:
+            y, hT, cT = Fn.lstm_bidirectional_residual(x, m.direction_params(0, False),
+                                                       m.direction_params(0, True), h0, c0)
+            return y, (hT, cT)
+        y, hT, cT = Fn.lstm_residual(x, *m.direction_params(0), None if h0 is None else h0[0],
+                                     None if c0 is None else c0[0])
+        return y, (hT.unsqueeze(0), cT.unsqueeze(0))
+
 
 class MHAMixer(Mixer):
     """Stack of MultiheadAttention layers; returns the last output tensor (mixer_block.py:255-305)."""
@@ -91,8 +106,9 @@ class MHAMixer(Mixer):
                              batch_first, nonlinearity, device=device, dtype=dtype)
             for _ in range(num_layers)])
 
-    def fused_residual_ln(self, ln, q, k, v, attn_mask=None):
-        """LN(MHA(q, k, v) + q) in one op (single layer, batch_first, k is v, reference mask)."""
+    def _fused_form(self, k, v, attn_mask):
+        """(mha, causal, qpad, kpad) when the mixer is the one attention op the fused residual forms
+        take (single layer, batch_first, k is v, no nonlinearity, reference mask), else None."""
         from .masks import BlockCausalMask
         if len(self.mixer) != 1 or k is not v or self.mixer[0].nonlinearity is not None:
             return None
@@ -104,9 +120,27 @@ class MHAMixer(Mixer):
         causal, qpad, kpad = False, None, None
         if attn_mask is not None:
             causal, qpad, kpad = True, attn_mask.main_pad, attn_mask.other_pad
+        return mha, causal, qpad, kpad
+
+    def fused_residual_ln(self, ln, q, k, v, attn_mask=None):
+        """LN(MHA(q, k, v) + q) in one op (single layer, batch_first, k is v, reference mask)."""
+        form = self._fused_form(k, v, attn_mask)
+        if form is None:
+            return None
+        mha, causal, qpad, kpad = form
         return Fn.mha_residual_layernorm(q, k, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
                                          mha.out_proj.bias, mha.num_heads, ln.weight, ln.bias, ln.eps,
                                          causal, qpad, kpad, dropout_p=mha.dropout if mha.training else 0.0)
+
+    def fused_residual(self, q, k, v, attn_mask=None):
+        """MHA(q, k, v) + q with q added by the output projection's GEMM (same forms as above)."""
+        form = self._fused_form(k, v, attn_mask)
+        if form is None:
+            return None
+        mha, causal, qpad, kpad = form
+        return Fn.mha_residual(q, k, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
+                               mha.out_proj.bias, mha.num_heads, causal, qpad, kpad,
+                               dropout_p=mha.dropout if mha.training else 0.0)
 
     def forward(self, q, k, v, attn_mask=None):
         if len(self.mixer) > 1:
@@ -177,6 +211,14 @@ class GRUMixer(Mixer):
 
     def forward(self, x, hn=None):
         return self.mixer(x, hn)
+
+    def fused_residual(self, x, hn=None):
+        """GRU(x) + x for one forward layer, as LSTMMixer.fused_residual (functional.gru_residual)."""
+        m = self.mixer
+        if not isinstance(x, torch.Tensor) or m.num_layers != 1 or m.bidirectional:
+            return None
+        y, hT = Fn.gru_residual(x, *m.direction_params(0), None if hn is None else hn[0])
+        return y, hT.unsqueeze(0)
 
 
 class LSTMMixerBlock(MixerBlock):

@@ -7,7 +7,7 @@ import torch
 from torch.autograd import Function
 
 from . import _lib, gemm_ops
-from .dense import _resln_bwd, _resln_fwd, residual_layernorm
+from .dense import _resln_bwd, _resln_fwd, residual_add, residual_layernorm
 from .gemm_ops import _dx_gemm, _fwd_gemm, _wgrad, _wt_note, colsum, gemm
 from .launch import _ARITH, _err_flag, _gbuf, _keeps_precision, _probe, _ptr, _stream, zeros
 from .wgrad_streams import beside_recurrence
@@ -299,6 +299,25 @@ def lstm_residual_layernorm(x, w_ih, w_hh, b_ih, b_hh, gamma, beta, eps=1e-5, h0
     return _LSTMFn.apply((1, False, (False,), force_bs, float(eps)), x, w_ih, w_hh, b_ih, b_hh, h0, c0, gamma, beta)
 
 
+def lstm_residual(x, w_ih, w_hh, b_ih, b_hh, h0=None, c0=None, force_bs=0):
+    """LSTM(x) + x for one unidirectional layer (In == H): ResidualConnection(LSTMMixer) without a
+    LayerNorm.  No GEMM feeds the sum (the recurrence writes y), so the add is one launch, over the
+    layer output where autograd does not keep it (residual_add).  Returns (y + x, hT, cT)."""
+    if x.shape[-1] != w_hh.shape[1]:
+        raise ValueError(f"lstm_residual: input size {x.shape[-1]} is not the hidden size {w_hh.shape[1]}")
+    y, hT, cT = lstm_layer(x, w_ih, w_hh, b_ih, b_hh, h0, c0, force_bs=force_bs)
+    return residual_add(y, x, inplace=True), hT, cT
+
+
+def lstm_bidirectional_residual(x, fw, bw, h0=None, c0=None, force_bs=0):
+    """The same around one bidirectional layer (In == 2H); arguments and states as
+    lstm_bidirectional_layer."""
+    if x.shape[-1] != 2 * fw[1].shape[1]:
+        raise ValueError(f"lstm_bidirectional_residual: input size {x.shape[-1]} is not 2 x {fw[1].shape[1]}")
+    y, hT, cT = lstm_bidirectional_layer(x, fw, bw, h0, c0, force_bs=force_bs)
+    return residual_add(y, x, inplace=True), hT, cT
+
+
 def lstm_layers_batched(problems: Sequence[Sequence], force_bs=0):
     """Several independent same-shape unidirectional layers in ONE persistent launch.
 
@@ -458,3 +477,11 @@ class _GRUFn(Function):
 def gru_layer(x, w_ih, w_hh, b_ih, b_hh, h0=None, reverse=False):
     """One direction of one nn.GRU layer (batch_first).  Returns (y, hT)."""
     return _GRUFn.apply(bool(reverse), x, w_ih, w_hh, b_ih, b_hh, h0)
+
+
+def gru_residual(x, w_ih, w_hh, b_ih, b_hh, h0=None):
+    """GRU(x) + x for one forward layer (In == H), as lstm_residual.  Returns (y + x, hT)."""
+    if x.shape[-1] != w_hh.shape[1]:
+        raise ValueError(f"gru_residual: input size {x.shape[-1]} is not the hidden size {w_hh.shape[1]}")
+    y, hT = gru_layer(x, w_ih, w_hh, b_ih, b_hh, h0)
+    return residual_add(y, x, inplace=True), hT
