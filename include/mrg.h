@@ -627,6 +627,39 @@ int mrg_grad_clip_norm(float* grads, long n, float max_norm, float* clip_state, 
                        hipStream_t stream);
 int mrg_grad_clip_value(float* grads, long n, float clip_value, hipStream_t stream);
 
+/* ---------------------------------------------------------------- gradient accumulation
+ * Lightning's trainer.accumulate_grad_batches = n inside the step launches, so that a captured step
+ * replays it.  accum: device int[2] = {micro, n}, n >= 1, owned by the caller.  A window is n
+ * consecutive step calls; the caller's backward passes sum into grads and nothing zeroes it inside a
+ * window.
+ *   calls 1 .. n-1 (micro + 1 < n)  every kernel reads accum (8 bytes) and returns: params, moments,
+ *       step_lr, clip_state and grads keep their bits; only micro advances.
+ *   call n (the boundary), in this order: grads becomes the mean grads / n; it is clipped as by the
+ *       plain entry points (clip_state[0] is the norm of the mean); the update is the plain step's,
+ *       operation for operation, on that mean; grads is zeroed; micro returns to 0 and step_lr[0]
+ *       advances by one, so bias correction and LR schedules count windows.
+ * A set err on the boundary skips the update and the step count as in mrg_adamw_step, and still zeroes
+ * grads and closes the window.  The 1 / n costs no pass of its own: mrg_grad_clip_norm_accum applies
+ * coef / n in its scale launch when it clips (coef < 1 or NaN) and leaves grads alone otherwise;
+ * mrg_grad_clip_value_accum computes clamp(g / n, -v, v).  The step is told what was done: prescaled
+ * != 0 after mrg_grad_clip_value_accum, clip_state (else null) after mrg_grad_clip_norm_accum, from
+ * which it reads whether that call clipped; with neither it divides by n itself (one rounded
+ * multiplication by 1.0f / n before anything else, so an unclipped window is bitwise the plain step on
+ * the sum times 1.0f / n).  mrg_*_step_accum must follow the clip call of its step in stream order:
+ * it is the launch that advances micro.  Grids depend on n (elements) alone.  Boundary traffic: the
+ * plain step's plus one 4-byte store per element, in place of a separate zero fill.               */
+int mrg_adamw_step_accum(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n,
+                         float* step_lr, float weight_decay, float beta1, float beta2, float eps,
+                         const int* err, int* accum, int prescaled, const float* clip_state,
+                         hipStream_t stream);
+int mrg_sgd_step_accum(float* params, float* grads, float* momentum_buf, long n, float* step_lr,
+                       float weight_decay, float momentum, const int* err, int* accum, int prescaled,
+                       const float* clip_state, hipStream_t stream);
+int mrg_grad_clip_norm_accum(float* grads, long n, float max_norm, float* clip_state, void* ws,
+                             const int* accum, hipStream_t stream);
+int mrg_grad_clip_value_accum(float* grads, long n, float clip_value, const int* accum,
+                              hipStream_t stream);
+
 /* ---------------------------------------------------------------- level schedule frame moves
  * Scheduled-sampling training of the lstmformer in dependence levels (ss_levels.py).  Tensors are
  * time-major, a frame is one [B][W] slab; idx / prev / teacher are device int32 [n].

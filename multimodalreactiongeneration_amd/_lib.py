@@ -200,6 +200,10 @@ SIGNATURES = {
     "mrg_grad_clip_workspace_bytes": (c_size, [c_long]),
     "mrg_grad_clip_norm": (c_int, [P, c_long, c_float, P, P, P]),
     "mrg_grad_clip_value": (c_int, [P, c_long, c_float, P]),
+    "mrg_adamw_step_accum": (c_int, [P, P, P, P, c_long, P, c_float, c_float, c_float, c_float, P, P, c_int, P, P]),
+    "mrg_sgd_step_accum": (c_int, [P, P, P, c_long, P, c_float, c_float, P, P, c_int, P, P]),
+    "mrg_grad_clip_norm_accum": (c_int, [P, c_long, c_float, P, P, P, P]),
+    "mrg_grad_clip_value_accum": (c_int, [P, c_long, c_float, P, P]),
     "mrg_frame_gather": (c_int, [c_int, c_int, c_int, P, P, P, P]),
     "mrg_frame_scatter": (c_int, [c_int, c_int, c_int, P, P, P, P]),
     "mrg_level_input": (c_int, [c_int, c_int, c_int, P, P, P, P, P, P]),

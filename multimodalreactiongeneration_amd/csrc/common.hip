@@ -16,7 +16,7 @@ void set_error(const char* fmt, ...) {
 
 MRG_API const char* mrg_last_error(void) { return mrg::g_err; }
 
-MRG_API int mrg_version(void) { return 107; }
+MRG_API int mrg_version(void) { return 108; }
 
 // Device query used by the host side to size persistent grids.
 MRG_API int mrg_device_cu_count(int device, int* out) {

@@ -126,6 +126,85 @@ __global__ __launch_bounds__(256) void gradclip_value_kernel(float* __restrict__
   gc_map<VEC>(g, n, GcClamp{v});
 }
 
+// ------------------------------------------------------------------ under gradient accumulation
+// Lightning's accumulate_grad_batches = n (the accum kernels of norm_loss_optim.hip): g holds the SUM of
+// the window's micro-batch gradients and accum = device int[2] {micro, n}.  Every launch below returns
+// after reading those 8 bytes unless this call closes the window (micro + 1 >= n), so off the boundary g
+// and clip_state keep their bits.  On the boundary they clip the MEAN g / n without a pass of its own:
+//   partial  as above, over the sum (same reads, same order of additions);
+//   final    norm = sqrt(sum g^2) / n in double, then the coefficient as above from that norm;
+//   scale    g *= coef / n when coef < 1 (or NaN), else nothing: a step that does not clip leaves the
+//            division to the update kernel, which reads the same coefficient and decides the same way;
+//   value    g = clamp(g / n, -v, v), always; the update kernel is told so (prescaled).
+__device__ __forceinline__ bool gc_off_boundary(const int* __restrict__ accum) {
+  return accum[0] + 1 < accum[1];
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void gradclip_sqsum_partial_accum_kernel(const float* __restrict__ g, long n,
+                                                                           float* __restrict__ part,
+                                                                           const int* __restrict__ accum) {
+  if (gc_off_boundary(accum)) return;   // uniform
+  float acc;
+  if (VEC) {
+    const long nv = n >> 2;
+    acc = gc_sqsum(reinterpret_cast<const float4*>(g), nv);
+    const long t = 4 * nv + (long)blockIdx.x * 256 + threadIdx.x;   // the n % 4 tail
+    if (t < n) acc = gc_sq(acc, g[t]);
+  } else {
+    acc = gc_sqsum(g, n);
+  }
+  __shared__ float red[4];
+  const float w = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void gradclip_final_accum_kernel(const float* __restrict__ part, int nblk,
+                                                                   float max_norm, float* __restrict__ clip_state,
+                                                                   const int* __restrict__ accum) {
+  if (gc_off_boundary(accum)) return;   // uniform
+  double s = 0.0;
+  for (int j = threadIdx.x; j < nblk; j += 256) s += (double)part[j];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float norm = (float)(sqrt((red[0] + red[1]) + (red[2] + red[3])) / (double)accum[1]);
+    const float c = max_norm / (norm + 1e-6f);
+    clip_state[0] = norm;
+    clip_state[1] = c > 1.0f ? 1.0f : c;
+  }
+}
+
+struct GcMeanClamp {
+  float s, v;
+  __device__ __forceinline__ float operator()(float x) const {
+    x *= s;
+    return x < -v ? -v : (x > v ? v : x);
+  }
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void gradclip_scale_accum_kernel(float* __restrict__ g, long n,
+                                                                   const float* __restrict__ clip_state,
+                                                                   const int* __restrict__ accum) {
+  if (gc_off_boundary(accum)) return;
+  const float c = clip_state[1];
+  if (c >= 1.0f) return;   // uniform: this window does not clip, the update divides by n
+  gc_map<VEC>(g, n, GcScale{c * (1.0f / (float)accum[1])});
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void gradclip_value_accum_kernel(float* __restrict__ g, long n, float v,
+                                                                   const int* __restrict__ accum) {
+  if (gc_off_boundary(accum)) return;
+  gc_map<VEC>(g, n, GcMeanClamp{1.0f / (float)accum[1], v});
+}
+
 static int gc_blocks(long n, int cap) {
   const long b = ((n + 3) / 4 + 255) / 256;   // one float4 per thread per sweep
   return (int)(b < cap ? (b < 1 ? 1 : b) : cap);
@@ -177,4 +256,45 @@ MRG_API int mrg_grad_clip_value(float* grads, long n, float clip_value, hipStrea
   else
     gradclip_value_kernel<false><<<mb, 256, 0, stream>>>(grads, n, clip_value);
   return check_launch("gradclip_value_kernel");
+}
+
+// The two above for a window of accumulated gradients (see "under gradient accumulation").  accum: device
+// int[2] = {micro, n}, read only.  Same grids as the plain entry points, on and off the boundary.
+MRG_API int mrg_grad_clip_norm_accum(float* grads, long n, float max_norm, float* clip_state, void* ws,
+                                     const int* accum, hipStream_t stream) {
+  MRG_REQUIRE(n >= 0, "mrg_grad_clip_norm_accum: n = %ld", n);
+  MRG_REQUIRE(max_norm >= 0.0f, "mrg_grad_clip_norm_accum: max_norm %g (must be >= 0, not NaN)",
+              (double)max_norm);
+  if (n == 0) return 0;
+  MRG_REQUIRE(grads && clip_state && ws && accum, "mrg_grad_clip_norm_accum: null pointer");
+  float* part = reinterpret_cast<float*>(ws);
+  const int nb = gc_blocks(n, GC_MAX_BLOCKS), mb = gc_blocks(n, GC_MAP_BLOCKS);
+  const bool vec = gc_aligned(grads);
+  if (vec)
+    gradclip_sqsum_partial_accum_kernel<true><<<nb, 256, 0, stream>>>(grads, n, part, accum);
+  else
+    gradclip_sqsum_partial_accum_kernel<false><<<nb, 256, 0, stream>>>(grads, n, part, accum);
+  if (check_launch("gradclip_sqsum_partial_accum_kernel")) return 1;
+  gradclip_final_accum_kernel<<<1, 256, 0, stream>>>(part, nb, max_norm, clip_state, accum);
+  if (check_launch("gradclip_final_accum_kernel")) return 1;
+  if (vec)
+    gradclip_scale_accum_kernel<true><<<mb, 256, 0, stream>>>(grads, n, clip_state, accum);
+  else
+    gradclip_scale_accum_kernel<false><<<mb, 256, 0, stream>>>(grads, n, clip_state, accum);
+  return check_launch("gradclip_scale_accum_kernel");
+}
+
+MRG_API int mrg_grad_clip_value_accum(float* grads, long n, float clip_value, const int* accum,
+                                      hipStream_t stream) {
+  MRG_REQUIRE(n >= 0, "mrg_grad_clip_value_accum: n = %ld", n);
+  MRG_REQUIRE(clip_value >= 0.0f, "mrg_grad_clip_value_accum: clip_value %g (must be >= 0, not NaN)",
+              (double)clip_value);
+  if (n == 0) return 0;
+  MRG_REQUIRE(grads && accum, "mrg_grad_clip_value_accum: null pointer");
+  const int mb = gc_blocks(n, GC_MAP_BLOCKS);
+  if (gc_aligned(grads))
+    gradclip_value_accum_kernel<true><<<mb, 256, 0, stream>>>(grads, n, clip_value, accum);
+  else
+    gradclip_value_accum_kernel<false><<<mb, 256, 0, stream>>>(grads, n, clip_value, accum);
+  return check_launch("gradclip_value_accum_kernel");
 }

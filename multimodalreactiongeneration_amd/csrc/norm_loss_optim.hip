@@ -593,6 +593,105 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
   }
 }
 
+// ------------------------------------------------------------------ gradient accumulation
+// Lightning's accumulate_grad_batches = n: the step launches of a window of n calls.  accum = device
+// int[2] {micro, n}: calls 1 .. n-1 (micro + 1 < n) return after reading those 8 bytes; call n, the
+// boundary, takes the mean of the summed micro-batch gradients (g / n), updates exactly as adamw_kernel /
+// sgd_kernel do from that value, and stores 0 to g for the next window.  A set err on the boundary skips
+// the update and still stores the zero: poisoned gradients do not leak into the next window.
+// Traffic on the boundary: the plain kernel's (AdamW 16 B read + 12 B written, SGD with momentum 12 + 8,
+// without 8 + 4 per element) plus the 4-B store of g, which replaces the separate fill of zero_grad().
+// The scale: 1 / n, unless the clipping pass of this step has folded it in already.  prescaled != 0: it
+// always has (value clipping).  clip_state != null: it has iff it clipped, i.e. the coefficient is not
+// >= 1 (norm clipping; gradclip_scale_accum_kernel decides by the same test).
+__device__ __forceinline__ bool accum_off_boundary(const int* __restrict__ accum) {
+  return accum[0] + 1 < accum[1];
+}
+
+__device__ __forceinline__ float accum_scale(const int* __restrict__ accum, int prescaled,
+                                             const float* __restrict__ clip_state) {
+  if (prescaled || (clip_state && !(clip_state[1] >= 1.0f))) return 1.0f;
+  return 1.0f / (float)accum[1];
+}
+
+// round(g * s), handed on as an opaque register: the compiler then sees the plain kernel's expressions on
+// a value it knows as little about as a load, and forms the plain kernel's instructions.  It must not
+// be contracted into the update's first addition, and with contraction alone switched off it was packed
+// with another product of the update (v_pk_mul_f32, which left wd * p rounded where sgd_kernel fuses it):
+// the step was then not the plain one on the averaged gradient bit for bit.
+__device__ __forceinline__ float accum_mean(float g, float s) {
+  float m = g * s;
+  asm volatile("" : "+v"(m));
+  return m;
+}
+
+__device__ __forceinline__ void accum_zero(float* __restrict__ g, long n) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) g[i] = 0.0f;
+}
+
+__global__ __launch_bounds__(256) void adamw_accum_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v, long n,
+                                                          const float* __restrict__ step_lr, float wd, float b1,
+                                                          float b2, float eps, const int* __restrict__ err,
+                                                          const int* __restrict__ accum, int prescaled,
+                                                          const float* __restrict__ clip_state) {
+  if (accum_off_boundary(accum)) return;
+  if (err && *err) return accum_zero(g, n);
+  const float s = accum_scale(accum, prescaled, clip_state);
+  float t = step_lr[0] + 1.0f;
+  float lr = step_lr[1];
+  float bc1 = 1.0f - powf(b1, t);
+  float bc2s = sqrtf(1.0f - powf(b2, t));
+  float step_size = lr / bc1;
+  float decay = 1.0f - lr * wd;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    float gi = accum_mean(g[i], s);
+    float pi = p[i] * decay;
+    float mi = m[i] + (1.0f - b1) * (gi - m[i]);
+    float vi = v[i] * b2 + (1.0f - b2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = pi - step_size * mi / (sqrtf(vi) / bc2s + eps);
+    g[i] = 0.0f;
+  }
+}
+
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_accum_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                        float* __restrict__ buf, long n,
+                                                        const float* __restrict__ step_lr, float wd, float mom,
+                                                        const int* __restrict__ err,
+                                                        const int* __restrict__ accum, int prescaled,
+                                                        const float* __restrict__ clip_state) {
+  if (accum_off_boundary(accum)) return;
+  if (err && *err) return accum_zero(g, n);
+  const float s = accum_scale(accum, prescaled, clip_state);
+  const bool first = step_lr[0] == 0.0f;
+  const float lr = step_lr[1];
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    float pi = p[i];
+    float gi = accum_mean(g[i], s) + wd * pi;
+    if (MOM) {
+      gi = first ? gi : mom * buf[i] + gi;
+      buf[i] = gi;
+    }
+    p[i] = pi - lr * gi;
+    g[i] = 0.0f;
+  }
+}
+
+// One thread, after the update in stream order: micro advances and wraps at n; the step count moves on a
+// boundary without error only, so bias correction and LR schedulers count windows.
+__global__ void accum_step_inc_kernel(float* step_lr, int* accum, const int* err) {
+  const int micro = accum[0] + 1;
+  if (micro < accum[1]) {
+    accum[0] = micro;
+    return;
+  }
+  accum[0] = 0;
+  if (!(err && *err)) step_lr[0] += 1.0f;
+}
+
 }  // namespace mrg
 
 using namespace mrg;
@@ -955,6 +1054,52 @@ MRG_API int mrg_sgd_step(float* params, const float* grads, float* momentum_buf,
   }
   adamw_step_inc_kernel<<<1, 1, 0, stream>>>(step_lr, err);
   return check_launch("adamw_step_inc_kernel");
+}
+
+// The steps under gradient accumulation (adamw_accum_kernel).  accum: device int[2] = {micro, n}, n >= 1,
+// advanced after the update.  grads is summed over the window by the caller's backward passes and is
+// zeroed on the boundary.  prescaled / clip_state (nullable): what the clipping pass of this step, if
+// any, has done about the 1 / n (mrg_grad_clip_value_accum: prescaled = 1; mrg_grad_clip_norm_accum: its
+// clip_state).  The grids are the plain steps': functions of n alone, on and off the boundary.
+MRG_API int mrg_adamw_step_accum(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n,
+                                 float* step_lr, float weight_decay, float beta1, float beta2, float eps,
+                                 const int* err, int* accum, int prescaled, const float* clip_state,
+                                 hipStream_t stream) {
+  MRG_REQUIRE(n >= 0, "mrg_adamw_step_accum: n = %ld", n);
+  MRG_REQUIRE(accum && step_lr, "mrg_adamw_step_accum: null accum or step_lr");
+  if (n > 0) {
+    MRG_REQUIRE(params && grads && exp_avg && exp_avg_sq, "mrg_adamw_step_accum: null pointer");
+    long nb = (n + 255) / 256;
+    int grid = (int)(nb < 4096 ? nb : 4096);
+    adamw_accum_kernel<<<grid, 256, 0, stream>>>(params, grads, exp_avg, exp_avg_sq, n, step_lr, weight_decay,
+                                                 beta1, beta2, eps, err, accum, prescaled, clip_state);
+    if (check_launch("adamw_accum_kernel")) return 1;
+  }
+  accum_step_inc_kernel<<<1, 1, 0, stream>>>(step_lr, accum, err);
+  return check_launch("accum_step_inc_kernel");
+}
+
+MRG_API int mrg_sgd_step_accum(float* params, float* grads, float* momentum_buf, long n, float* step_lr,
+                               float weight_decay, float momentum, const int* err, int* accum, int prescaled,
+                               const float* clip_state, hipStream_t stream) {
+  MRG_REQUIRE(n >= 0, "mrg_sgd_step_accum: n = %ld", n);
+  MRG_REQUIRE(accum && step_lr, "mrg_sgd_step_accum: null accum or step_lr");
+  MRG_REQUIRE(momentum == 0.0f || momentum_buf != nullptr || n == 0,
+              "mrg_sgd_step_accum: momentum %g needs a momentum buffer", (double)momentum);
+  if (n > 0) {
+    MRG_REQUIRE(params && grads, "mrg_sgd_step_accum: null pointer");
+    long nb = (n + 255) / 256;
+    int grid = (int)(nb < 4096 ? nb : 4096);
+    if (momentum != 0.0f)
+      sgd_accum_kernel<true><<<grid, 256, 0, stream>>>(params, grads, momentum_buf, n, step_lr, weight_decay,
+                                                       momentum, err, accum, prescaled, clip_state);
+    else
+      sgd_accum_kernel<false><<<grid, 256, 0, stream>>>(params, grads, nullptr, n, step_lr, weight_decay, 0.0f,
+                                                        err, accum, prescaled, clip_state);
+    if (check_launch("sgd_accum_kernel")) return 1;
+  }
+  accum_step_inc_kernel<<<1, 1, 0, stream>>>(step_lr, accum, err);
+  return check_launch("accum_step_inc_kernel");
 }
 
 // ------------------------------------------------------------------ padding helpers

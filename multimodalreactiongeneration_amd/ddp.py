@@ -17,6 +17,15 @@ The number of writes per parameter is taken from a first, non-overlapped census
 backward (the graph is static, as DDP's ``static_graph``); every rank runs the
 same graph, so the buckets complete in the same order everywhere (RCCL needs one
 collective order on all ranks).  ``finish()`` makes the current stream wait.
+
+Gradient accumulation (``optimizer=`` an optimizer with ``accumulate_grad_batches = n > 1``): the
+reducer exchanges once per window, after the backward pass that the window's last ``step()`` follows,
+and does nothing after the others (Lightning's ``no_sync``): the ranks' sums are averaged once, the
+optimizer then divides by n.  Which call that is the host has to know, since the all-reduce is issued
+by the host: it asks ``optimizer.closes_window()``, the optimizer's own count of its eager ``step()``
+calls.  No step with an all-reduce in it is captured into a graph here (bench.py replays forward and
+backward and issues the exchange and the update eagerly); an optimizer whose ``step()`` was captured
+cannot say which replay closes a window, and the reducer then raises instead of guessing.
 """
 from __future__ import annotations
 
@@ -100,12 +109,16 @@ class GradReducer:
     """Average a flat gradient buffer across ranks, in buckets, on a side stream.
 
     ``comm``: None = torch.distributed (backend "nccl" is RCCL), or a ``NativeComm`` (libmrg's
-    own RCCL communicator, the ``mrg_comm_*`` C-ABI)."""
+    own RCCL communicator, the ``mrg_comm_*`` C-ABI).  ``optimizer``: the fused optimizer that owns
+    ``flat_grad``, needed only when it accumulates gradients: the exchange then runs once per window.
+    ``exchanges`` counts the backward passes whose gradients were exchanged."""
 
     def __init__(self, flat_grad: torch.Tensor, bucket_elems: int = 0, params=None, overlap: bool = False,
-                 bucket_bytes: int = 8 << 20, comm: "NativeComm" = None):
+                 bucket_bytes: int = 8 << 20, comm: "NativeComm" = None, optimizer=None):
         self.flat_grad = flat_grad
         self.comm = comm
+        self.optimizer = optimizer
+        self.exchanges = 0
         self.world = comm.world if comm is not None else (dist.get_world_size() if dist.is_initialized() else 1)
         self.backend = dist.get_backend() if dist.is_initialized() else None
         n = flat_grad.numel()
@@ -193,11 +206,17 @@ class GradReducer:
                 self._launch(b)
         self._task = None
 
+    def _exchange_now(self):
+        """False inside an accumulation window: the gradients go on summing locally."""
+        return self.optimizer is None or self.optimizer.closes_window()
+
     def _launch(self, b):
         from .wgrad_streams import side_stream
         s, e = self.buckets[b]
         self.launched[b] = True
         self.order.append(b)
+        if not self._exchange_now():
+            return
         op, scale = self._op()
         dev = self.flat_grad.device
         if self.stream is not None:
@@ -229,6 +248,9 @@ class GradReducer:
             return
         if not self.overlap:
             return self.allreduce()
+        if not self._exchange_now():
+            return
+        self.exchanges += 1
         self._agree_error_flag()
         if self.stream is not None:
             torch.cuda.current_stream(self.flat_grad.device).wait_stream(self.stream)
@@ -270,6 +292,9 @@ class GradReducer:
             return
         if self.overlap:
             return self.finish()
+        if not self._exchange_now():
+            return
+        self.exchanges += 1
         op, scale = self._op()
         if self.comm is not None:
             cur = torch.cuda.current_stream(self.flat_grad.device)

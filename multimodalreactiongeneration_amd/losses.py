@@ -48,12 +48,20 @@ def clip_grad_workspace(n: int, device) -> torch.Tensor:
     return torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=device)
 
 
+def _accum_i32(accum: torch.Tensor, who: str):
+    if not (accum.is_cuda and accum.dtype == torch.int32 and accum.is_contiguous() and accum.numel() >= 2):
+        raise ValueError(f"functional.{who}: accum must be a contiguous device int32[2] = {{micro, n}}")
+
+
 def clip_grad_norm_(flat_grad: torch.Tensor, max_norm: float, clip_state: Optional[torch.Tensor] = None,
-                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    workspace: Optional[torch.Tensor] = None, accum: Optional[torch.Tensor] = None) -> torch.Tensor:
     """torch.nn.utils.clip_grad_norm_(norm_type=2, error_if_nonfinite=False) over one buffer, in place
     (mrg_grad_clip_norm).  Returns clip_state, a device float32[2] = {norm before clipping, coefficient
     applied}; nothing is read back.  max_norm = inf only measures.  clip_state / workspace
-    (clip_grad_workspace) may be passed in so that the call allocates nothing."""
+    (clip_grad_workspace) may be passed in so that the call allocates nothing.
+    accum (an optimizer's accum_state, device int32 {micro, n}): the buffer holds a window's summed
+    gradients; the call does nothing unless it closes the window, and then clips their mean
+    (mrg_grad_clip_norm_accum; the fused step that follows must be given the same clip_state)."""
     _flat_f32(flat_grad, "clip_grad_norm_")
     if clip_state is None:
         clip_state = zeros(2, device=flat_grad.device)
@@ -64,14 +72,27 @@ def clip_grad_norm_(flat_grad: torch.Tensor, max_norm: float, clip_state: Option
     if workspace is None:
         workspace = clip_grad_workspace(n, flat_grad.device)
         hold_scratch(workspace)
+    if accum is not None:
+        _accum_i32(accum, "clip_grad_norm_")
+        _lib.check(_lib.load().mrg_grad_clip_norm_accum(_ptr(flat_grad), n, float(max_norm), _ptr(clip_state),
+                                                        _ptr(workspace), _ptr(accum), _stream()),
+                   "grad clip norm (accumulation)")
+        return clip_state
     _lib.check(_lib.load().mrg_grad_clip_norm(_ptr(flat_grad), n, float(max_norm), _ptr(clip_state),
                                               _ptr(workspace), _stream()), "grad clip norm")
     return clip_state
 
 
-def clip_grad_value_(flat_grad: torch.Tensor, clip_value: float) -> torch.Tensor:
-    """torch.clamp(g, -clip_value, clip_value) in place (mrg_grad_clip_value); a NaN stays NaN."""
+def clip_grad_value_(flat_grad: torch.Tensor, clip_value: float, accum: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """torch.clamp(g, -clip_value, clip_value) in place (mrg_grad_clip_value); a NaN stays NaN.
+    accum: as in clip_grad_norm_; on the call that closes the window, clamp(g / n, -clip_value, clip_value)
+    (mrg_grad_clip_value_accum; the fused step that follows must be told the division is done)."""
     _flat_f32(flat_grad, "clip_grad_value_")
+    if accum is not None:
+        _accum_i32(accum, "clip_grad_value_")
+        _lib.check(_lib.load().mrg_grad_clip_value_accum(_ptr(flat_grad), flat_grad.numel(), float(clip_value),
+                                                         _ptr(accum), _stream()), "grad clip value (accumulation)")
+        return flat_grad
     _lib.check(_lib.load().mrg_grad_clip_value(_ptr(flat_grad), flat_grad.numel(), float(clip_value), _stream()),
                "grad clip value")
     return flat_grad

@@ -99,7 +99,8 @@ class LightningSurface(nn.Module):
     def _optimizers(self, optim):
         # Lightning's Trainer keys, read from the optim mapping: there is no Trainer here
         clip = dict(gradient_clip_val=optim.get("gradient_clip_val"),
-                    gradient_clip_algorithm=optim.get("gradient_clip_algorithm", "norm"))
+                    gradient_clip_algorithm=optim.get("gradient_clip_algorithm", "norm"),
+                    accumulate_grad_batches=optim.get("accumulate_grad_batches", 1))
         if optim.use_optimizer == "adam":
             opt = FusedAdamW(self.parameters(), lr=optim.lr, weight_decay=optim.weight_decay, **clip)
         elif optim.use_optimizer == "sgd":

@@ -17,6 +17,12 @@ timeout; the update kernel reads it and skips the update (garbage gradients neve
 reach the weights, replayed graphs included), and ``step()`` raises at the next
 step once the flag, copied to pinned host memory without a sync, reads non-zero.
 
+Gradient accumulation (Lightning's ``accumulate_grad_batches = n``): a window is ``n`` consecutive
+``step()`` calls with a backward pass before each and no ``zero_grad()`` in between, so the gradients sum
+in ``flat_grad``.  Calls 1 .. n-1 change nothing but a micro-step counter on the device; call n takes the
+mean, clips it, updates, zeroes ``flat_grad`` and counts one step.  The counter sits beside ``step_lr``
+and the kernels branch on it themselves, so one captured ``step()`` replays a whole window correctly.
+
 Checkpoints: ``state_dict()`` / ``load_state_dict()`` speak the layout of the torch
 optimizer of the same name (per-parameter entries keyed by the parameter's index),
 sliced out of / copied into the flat buffers, so a Lightning ``optimizer_states``
@@ -58,6 +64,11 @@ def _check_clipping(val, algorithm):
         raise ValueError(f"gradient_clip_val {val!r}: None, 0 (off) or a positive number")
 
 
+def _check_accumulation(n):
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"accumulate_grad_batches {n!r}: an int >= 1")
+
+
 class _LRGroup(dict):
     """A param group whose 'lr' assignment (LR schedulers) is mirrored to the device buffer."""
 
@@ -81,9 +92,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
     _UPDATE = ""
 
-    def __init__(self, params: Iterable, defaults, gradient_clip_val=None, gradient_clip_algorithm="norm"):
+    def __init__(self, params: Iterable, defaults, gradient_clip_val=None, gradient_clip_algorithm="norm",
+                 accumulate_grad_batches=1):
         params = list(params)
         _check_clipping(gradient_clip_val, gradient_clip_algorithm)   # before the parameters are re-pointed
+        _check_accumulation(accumulate_grad_batches)
         super().__init__(params, defaults)
         if len(self.param_groups) != 1:
             raise ValueError(f"{type(self).__name__} takes one param group (one flat buffer, one device-side LR)")
@@ -97,6 +110,68 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._err_host = self._err_event = None
         self.clip_state = self._clip_ws = None
         self.set_gradient_clipping(gradient_clip_val, gradient_clip_algorithm)
+        self.accum_state = None
+        self.set_accumulation(accumulate_grad_batches)
+
+    # ---- gradient accumulation (Lightning's trainer.accumulate_grad_batches).  An attribute of the
+    # optimizer like clipping: not a group option, not in state_dict(), left alone by load_state_dict().
+    def set_accumulation(self, n):
+        """Update once per window of ``n`` ``step()`` calls, on the mean of the gradients the backward passes
+        of the window summed into ``flat_grad`` (1: every call updates, the default).  ``step()`` zeroes
+        ``flat_grad`` when it closes a window; calling ``zero_grad()`` inside a window discards the
+        micro-batches summed so far and is not checked for.  Changing ``n`` restarts the window.  The device
+        counter is allocated here, never in ``step()``, so call it before a step is captured into a graph."""
+        _check_accumulation(n)
+        if self.flat.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("set_accumulation inside a graph capture: a captured step holds the "
+                               "launches it was recorded with; set it before graphs.capture")
+        self.accumulate_grad_batches = n
+        self._micro_host = 0   # the host's count of step() calls in the window (ddp.GradReducer reads it)
+        if n > 1 or self.accum_state is not None:   # once allocated it stays: a captured step may hold its address
+            state = torch.tensor([0, n], dtype=torch.int32)
+            if self.accum_state is None:
+                self.accum_state = state.to(self.flat.device)
+            else:
+                self.accum_state.copy_(state)
+
+    @property
+    def micro_step(self):
+        """0-d device view: the step() calls made in the current window, 0 .. n-1 (no sync)."""
+        if self.accum_state is None:
+            raise RuntimeError("micro_step: accumulation is off (accumulate_grad_batches=1)")
+        return self.accum_state[0]
+
+    def closes_window(self):
+        """Whether the next ``step()`` updates (True without accumulation).  Counted on the host from the
+        ``step()`` calls made here, for what the host has to decide itself (the DDP all-reduce); a step
+        that was captured into a graph advances the device counter only, and then this refuses."""
+        if self.accumulate_grad_batches == 1:
+            return True
+        if self._micro_host is None:
+            raise RuntimeError("accumulate_grad_batches > 1 with a step() captured into a graph: the host "
+                               "cannot tell which replay closes a window (ddp.GradReducer needs an eager "
+                               "step(); call set_accumulation to start over)")
+        return self._micro_host == self.accumulate_grad_batches - 1
+
+    def _accum_begin(self):
+        """An accumulating step: clip launches first, then what the update has to know about the 1 / n
+        (prescaled, clip_state) as mrg_*_step_accum takes it.  Advances the host's mirror."""
+        if self.flat.is_cuda and torch.cuda.is_current_stream_capturing():
+            self._micro_host = None
+        elif self._micro_host is not None:
+            self._micro_host = (self._micro_host + 1) % self.accumulate_grad_batches
+        if not self.gradient_clip_val:
+            return 0, None
+        from . import functional as Fn
+        if self.gradient_clip_algorithm == "norm":
+            Fn.clip_grad_norm_(self.flat_grad, self.gradient_clip_val, self.clip_state, self._clip_ws,
+                               accum=self.accum_state)
+            return 0, self.clip_state
+        Fn.clip_grad_value_(self.flat_grad, self.gradient_clip_val, accum=self.accum_state)
+        return 1, None
+
+    def _state_tensors(self, *tensors):
+        return [t for t in tensors + (self.accum_state,) if t is not None]
 
     # ---- gradient clipping (Lightning's trainer.gradient_clip_val / gradient_clip_algorithm).  Attributes
     # of the optimizer, as they are the Trainer's there: not a group option, not in state_dict().
@@ -278,10 +353,10 @@ class FusedAdamW(_FlatOptimizer):
     _UPDATE = "AdamW"
 
     def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 gradient_clip_val=None, gradient_clip_algorithm="norm"):
+                 gradient_clip_val=None, gradient_clip_algorithm="norm", accumulate_grad_batches=1):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                                       maximize=False, decoupled_weight_decay=True),
-                         gradient_clip_val, gradient_clip_algorithm)
+                         gradient_clip_val, gradient_clip_algorithm, accumulate_grad_batches)
         self.exp_avg = torch.zeros_like(self.flat)
         self.exp_avg_sq = torch.zeros_like(self.flat)
 
@@ -305,15 +380,24 @@ class FusedAdamW(_FlatOptimizer):
 
     def state_tensors(self):
         """Device state one update changes (graphs.capture(preserve=...) restores it after warm-up)."""
-        return [self.flat, self.exp_avg, self.exp_avg_sq, self.step_lr]
+        return self._state_tensors(self.flat, self.exp_avg, self.exp_avg_sq, self.step_lr)
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         g = self._begin_step()
+        b1, b2 = g["betas"]
+        if self.accumulate_grad_batches > 1:
+            prescaled, clip_state = self._accum_begin()
+            _lib.check(_lib.load().mrg_adamw_step_accum(
+                _ptr(self.flat), _ptr(self.flat_grad), _ptr(self.exp_avg), _ptr(self.exp_avg_sq),
+                self.flat.numel(), _ptr(self.step_lr), float(g["weight_decay"]), float(b1), float(b2),
+                float(g["eps"]), _ptr(_err_flag(self.flat.device)), _ptr(self.accum_state), prescaled,
+                _ptr(clip_state), _stream()), "adamw (accumulation)")
+            self._end_step()
+            return loss
         if self.gradient_clip_val:
             self._clip_gradients()
-        b1, b2 = g["betas"]
         _lib.check(_lib.load().mrg_adamw_step(
             _ptr(self.flat), _ptr(self.flat_grad), _ptr(self.exp_avg), _ptr(self.exp_avg_sq),
             self.flat.numel(), _ptr(self.step_lr), float(g["weight_decay"]), float(b1), float(b2),
@@ -328,10 +412,10 @@ class FusedSGD(_FlatOptimizer):
     _UPDATE = "SGD"
 
     def __init__(self, params: Iterable, lr, momentum=0.0, weight_decay=0.0, dampening=0.0, nesterov=False,
-                 maximize=False, gradient_clip_val=None, gradient_clip_algorithm="norm"):
+                 maximize=False, gradient_clip_val=None, gradient_clip_algorithm="norm", accumulate_grad_batches=1):
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                                       nesterov=nesterov, maximize=maximize),
-                         gradient_clip_val, gradient_clip_algorithm)
+                         gradient_clip_val, gradient_clip_algorithm, accumulate_grad_batches)
         self.momentum_buf = None
         self._fit_moments(self.param_groups[0])
 
@@ -359,12 +443,21 @@ class FusedSGD(_FlatOptimizer):
 
     def state_tensors(self):
         """Device state one update changes (graphs.capture(preserve=...) restores it after warm-up)."""
-        return [t for t in (self.flat, self.momentum_buf, self.step_lr) if t is not None]
+        return self._state_tensors(self.flat, self.momentum_buf, self.step_lr)
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         g = self._begin_step()
+        if self.accumulate_grad_batches > 1:
+            prescaled, clip_state = self._accum_begin()
+            _lib.check(_lib.load().mrg_sgd_step_accum(
+                _ptr(self.flat), _ptr(self.flat_grad), _ptr(self.momentum_buf), self.flat.numel(),
+                _ptr(self.step_lr), float(g["weight_decay"]), float(g["momentum"]),
+                _ptr(_err_flag(self.flat.device)), _ptr(self.accum_state), prescaled, _ptr(clip_state),
+                _stream()), "sgd (accumulation)")
+            self._end_step()
+            return loss
         if self.gradient_clip_val:
             self._clip_gradients()
         _lib.check(_lib.load().mrg_sgd_step(
