@@ -460,6 +460,36 @@ int mrg_attention_bwd_dropout(int B, int heads, int Tq, int Tk, int D,
                               float* dv, long dv_bs, long dv_ts, float* workspace, unsigned int thr,
                               float scale_keep, const unsigned long long* key, hipStream_t stream);
 
+/* nn.MultiheadAttention(add_bias_kv / add_zero_attn): the extra keys every query sees, after the Tk
+ * real ones in the order [bias key, zero key], merged into the result of the calls above
+ * (csrc/attention_extra.hip).  bias_k / bias_v: [heads * D], both or neither; zero_attn != 0: the
+ * all-zero key and value.  q / o / dout / dq as above (rows of heads * D <= 1024 floats; float4 where
+ * every row is 16-B aligned, a scalar form otherwise); lse is the plain [B, heads, Tq] array (no
+ * chunk form).  rkey nullable: the op's dropout key, thr / keep_scale as above; the bias key is
+ * attention column Tk of the index map.
+ * fwd: after mrg_attention_fwd(_dropout): o <- w_main o + w1 keep bias_v and lse <- lse_tot, in place.
+ * A row the main call found fully masked (lse NaN) becomes bias_v (bias key only), w1 bias_v, or 0.
+ * bwd: after mrg_attention_bwd(_dropout) on the merged o / lse: dq += the bias key's share, dbias_k /
+ * dbias_v [heads * D] stored (accumulate = 0) or added to (1), deterministic.  Needs bias_k / bias_v
+ * (the zero key has no gradient).  pk / lse_main / cbuf, all or none and only with rkey: the dropout
+ * backward's delta lacks the bias key's term c; pk / lse_main are o / lse of mrg_attention_fwd with
+ * v = k, the call subtracts scale c w_main pk from dq and writes c to cbuf [B, heads, Tq], and
+ * mrg_attention_bwd_chunk(passes = 2, kv_accumulate = 1, dout = zeros, workspace = cbuf) then
+ * subtracts the term from dk.                                                                      */
+int mrg_attention_extra_fwd(int B, int heads, int Tq, int D, const float* q, long q_bs, long q_ts,
+                            const float* bias_k, const float* bias_v, int zero_attn, float scale,
+                            float* o, long o_bs, long o_ts, float* lse, int Tk, unsigned int thr,
+                            float keep_scale, const unsigned long long* rkey, hipStream_t stream);
+size_t mrg_attention_extra_bwd_workspace_bytes(int B, int heads, int Tq, int D);
+int mrg_attention_extra_bwd(int B, int heads, int Tq, int D, const float* q, long q_bs, long q_ts,
+                            const float* bias_k, const float* bias_v, float scale,
+                            const float* o, long o_bs, long o_ts, const float* lse,
+                            const float* dout, long do_bs, long do_ts, float* dq, long dq_bs, long dq_ts,
+                            float* dbias_k, float* dbias_v, int accumulate, int Tk, unsigned int thr,
+                            float keep_scale, const unsigned long long* rkey,
+                            const float* pk, long pk_bs, long pk_ts, const float* lse_main, float* cbuf,
+                            float* workspace, hipStream_t stream);
+
 /* ---------------------------------------------------------------- LayerNorm
  * y = LayerNorm(a + b) (ResidualConnection.forward, residual_connection.py:
  * 20-37), rows x E, 1 <= E <= 1024; mean/rstd saved per row.     */

@@ -7,7 +7,7 @@ from torch.autograd import Function
 from . import _lib
 from .dense import _resln_bwd, _resln_fwd
 from .gemm_ops import _dx_gemm, _fwd_gemm, _wgrad, _wt_note, gemm
-from .launch import _flush_touched, _gbuf, _keeps_precision, _probe, _ptr, _stream, _ws
+from .launch import _flush_touched, _gbuf, _keeps_precision, _probe, _ptr, _stream, _ws, zeros
 
 # --- dropout RNG (csrc/rng.h, rng.py): a per-device {seed, draw} state in device memory.  An op that
 # drops takes one draw with a one-thread kernel (a graph node: a replayed step takes fresh draws) and
@@ -147,7 +147,8 @@ def _attn_args(heads, Q, KV, O, lse, qpad, kpad, causal, scale):
 class _MHAFn(Function):
     @staticmethod
     @_keeps_precision
-    def forward(ctx, spec, q_in, kv_in, in_w, in_b, out_w, out_b, qpad, kpad, gamma=None, beta=None):
+    def forward(ctx, spec, q_in, kv_in, in_w, in_b, out_w, out_b, qpad, kpad, gamma=None, beta=None,
+                bias_k=None, bias_v=None):
         # eps not None: return LN(attn + q) (ResidualConnection(MHAMixer)); p > 0: dropout on the
         # attention probabilities with one draw, the key saved for the backward
         # addq: return attn + q (the residual without a LayerNorm), q added by the output projection's
@@ -155,6 +156,9 @@ class _MHAFn(Function):
         heads, causal, eps, *rest = spec
         p = rest[0] if rest else 0.0
         addq = bool(rest[1]) if len(rest) > 1 else False
+        # extra always-visible keys (add_bias_kv: bias_k / bias_v; add_zero_attn: rest[2]): one merge launch
+        # after the attention kernel (_extra_fwd)
+        zero_attn = bool(rest[2]) if len(rest) > 2 else False
         _lib.require_device(q_in)
         dev = q_in.device
         B, Tq, E = q_in.shape
@@ -180,6 +184,8 @@ class _MHAFn(Function):
             with _probe("attn_fwd", 4.0 * D * B * heads * visible_pairs(Tq, Tk, causal)):
                 rc = lib.mrg_attention_fwd(*args, _stream())
         _lib.check(rc, "attention fwd")
+        if bias_k is not None or zero_attn:
+            _extra_fwd(heads, Q, bias_k, bias_v, zero_attn, scale, O, lse, Tk, drop)
         out = torch.empty(B, Tq, E, device=dev, dtype=torch.float32)
         kw = dict(epi=3, aux=_ptr(q2), ldaux=E) if addq else {}
         _fwd_gemm(B * Tq, E, E, _ptr(O), E, out_w, _ptr(out), E, bias=_ptr(out_b), device=dev, **kw)
@@ -194,7 +200,10 @@ class _MHAFn(Function):
             u, mean, rstd = _resln_fwd(out.view(B * Tq, E), q2.view(B * Tq, E), gamma, beta, eps)
             res = u.view(B, Tq, E)
             extra = [out, gamma, beta, mean, rstd]
+        if bias_k is not None:
+            extra = extra + [bias_k, bias_v]
         ctx.save_for_backward(q2, kv2, Q, KV, O, lse, in_w, in_b, out_w, out_b, qpad, kpad, *extra)
+        ctx.has_bias_kv = bias_k is not None
         ctx.spec = (heads, causal, scale, eps is not None)
         ctx.addq = addq
         ctx.drop = drop
@@ -213,7 +222,7 @@ class _MHAFn(Function):
         lib = _lib.load()
         g = None  # residual-branch gradient of LN(attn + q), added by the dq GEMM's epilogue
         if resln:
-            out, gamma, beta, mean, rstd = saved[12:]
+            out, gamma, beta, mean, rstd = saved[12:17]
             g = _resln_bwd(dout.reshape(B * Tq, E).contiguous(), out.view(B * Tq, E), q2.view(B * Tq, E),
                            gamma, beta, mean, rstd)
             do2 = g.view(B, Tq, E)
@@ -237,6 +246,8 @@ class _MHAFn(Function):
             with _probe("attn_bwd", 10.0 * D * B * heads * visible_pairs(Tq, Tk, causal)):
                 rc = lib.mrg_attention_bwd(*args, _stream())
         _lib.check(rc, "attention bwd")
+        if ctx.has_bias_kv:   # the zero key alone has no gradient: the merged O / lse did it all
+            _extra_bwd(heads, Q, KV, O, lse, qpad, kpad, causal, scale, saved[-2:], dO, dQ, dKV, ctx.drop)
         gw, gb = _gbuf(in_w), _gbuf(in_b)
         _wgrad(_ptr(dQ), E, _ptr(q2), E, B * Tq, E, E, None if gw is None else gw[:E], dev,
                gb=None if gb is None else gb[:E], keep=(dQ, q2))
@@ -250,7 +261,56 @@ class _MHAFn(Function):
         if ctx.needs_input_grad[2]:
             dkv_in = torch.empty(B, Tk, E, device=dev, dtype=torch.float32)
             _dx_gemm(B * Tk, E, 2 * E, _ptr(dKV), 2 * E, in_w[E:], _ptr(dkv_in), E, device=dev)
-        return None, dq_in, dkv_in, None, None, None, None, None, None, None, None
+        return None, dq_in, dkv_in, None, None, None, None, None, None, None, None, None, None
+
+
+def _extra_fwd(heads, Q, bias_k, bias_v, zero_attn, scale, O, lse, Tk, drop):
+    """Merge the extra keys into the attention kernel's O / lse in place (mrg_attention_extra_fwd)."""
+    B, Tq, E = Q.shape
+    thr, sk, key = drop if drop is not None else (0, 1.0, None)
+    _lib.check(_lib.load().mrg_attention_extra_fwd(
+        B, heads, Tq, E // heads, _ptr(Q), Tq * E, E, _ptr(bias_k), _ptr(bias_v), int(zero_attn), scale,
+        _ptr(O), Tq * E, E, _ptr(lse), Tk, thr, sk, _ptr(key), _stream()), "attention extra keys fwd")
+
+
+def _extra_bwd(heads, Q, KV, O, lse, qpad, kpad, causal, scale, bias_kv, dO, dQ, dKV, drop):
+    """The bias key's share of the gradients, after the attention backward on the merged O / lse: dQ
+    gets its term in place, bias_k.grad / bias_v.grad theirs (mrg_attention_extra_bwd).  The dropout
+    backward forms delta from the main keys' own terms, so there the bias key's term c is missing
+    from dQ and dK: a forward call with V = K gives sum_k P_k K_k for the dQ term, and the dK / dV
+    pass alone (dO = 0, c in the delta rows, accumulating) subtracts the dK term (include/mrg.h)."""
+    bias_k, bias_v = bias_kv
+    B, Tq, E = Q.shape
+    Tk = KV.shape[1]
+    D = E // heads
+    dev = Q.device
+    lib = _lib.load()
+    gk, gv = _gbuf(bias_k), _gbuf(bias_v)
+    acc = 1
+    if gk is None or gv is None:   # frozen: the kernel still needs somewhere to write
+        gk, gv, acc = torch.empty(E, device=dev), torch.empty(E, device=dev), 0
+    ws = _ws(lib.mrg_attention_extra_bwd_workspace_bytes(B, heads, Tq, D), dev)
+    thr, sk, key = drop if drop is not None else (0, 1.0, None)
+    pk = lse_main = cbuf = None
+    if drop is not None and Tk > 0:
+        pk = torch.empty(B, Tq, E, device=dev, dtype=torch.float32)
+        lse_main = torch.empty(B, heads, Tq, device=dev, dtype=torch.float32)
+        cbuf = torch.empty(B, heads, Tq, device=dev, dtype=torch.float32)
+        _lib.check(lib.mrg_attention_fwd(B, heads, Tq, Tk, D, _ptr(Q), Tq * E, E, _ptr(KV), Tk * 2 * E, 2 * E,
+                                         _ptr(KV), Tk * 2 * E, 2 * E, _ptr(pk), Tq * E, E, _ptr(lse_main),
+                                         _ptr(qpad), _ptr(kpad), int(causal), scale, _stream()),
+                   "attention extra keys: P K")
+    _lib.check(lib.mrg_attention_extra_bwd(
+        B, heads, Tq, D, _ptr(Q), Tq * E, E, _ptr(bias_k), _ptr(bias_v), scale, _ptr(O), Tq * E, E, _ptr(lse),
+        _ptr(dO), Tq * E, E, _ptr(dQ), Tq * E, E, _ptr(gk), _ptr(gv), acc, Tk, thr, sk, _ptr(key),
+        _ptr(pk), Tq * E, E, _ptr(lse_main), _ptr(cbuf), _ptr(ws), _stream()), "attention extra keys bwd")
+    if cbuf is not None:
+        z = zeros(E, device=dev)   # dO = 0 for every query: one row, strides 0
+        _lib.check(lib.mrg_attention_bwd_chunk(
+            B, heads, Tq, Tk, D, 0, Tq, _ptr(Q), Tq * E, E, _ptr(KV), Tk * 2 * E, 2 * E, _ptr(KV, E), Tk * 2 * E,
+            2 * E, _ptr(O), Tq * E, E, _ptr(lse), _ptr(qpad), _ptr(kpad), int(causal), scale, _ptr(z), 0, 0,
+            _ptr(dQ), Tq * E, E, _ptr(dKV), Tk * 2 * E, 2 * E, _ptr(dKV, E), Tk * 2 * E, 2 * E, 2, 1, _ptr(cbuf),
+            _stream()), "attention extra keys: dK delta term")
 
 
 class _MHAOneKeyFn(Function):
@@ -331,13 +391,28 @@ def _one_key(q, kv):
 
 
 def _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
-         eps=None, ln=(), addq=False):
+         eps=None, ln=(), addq=False, bias_k=None, bias_v=None, add_zero_attn=False):
     """The attention Function for these shapes; eps not None: LN(. + q) with ln = (gamma, beta); addq:
-    . + q without a LayerNorm."""
+    . + q without a LayerNorm.  bias_k / bias_v ([1, 1, E] or [E]; both or neither) and add_zero_attn:
+    nn.MultiheadAttention's extra keys, visible to every query whatever the mask rules say.  With one the
+    call is always the unchunked _MHAFn: the one-key form does not apply (there is more than one key),
+    and the query-chunked schedules (encoder_stack, integrate) never see such a module
+    (forms.integrator_form declines it), so the merge has no chunk form."""
     if in_proj_weight.shape[0] != 3 * q.shape[-1]:
         raise ValueError("in_proj_weight must be [3E, E]")
     p = float(dropout_p)
     _drop_consts(p)
+    if (bias_k is None) != (bias_v is None):
+        raise ValueError("mha: bias_k and bias_v come together")
+    if bias_k is not None or add_zero_attn:
+        E = q.shape[-1]
+        for t in (bias_k, bias_v):
+            if t is not None and (t.numel() != E or t.dtype != torch.float32 or not t.is_contiguous()
+                                  or t.device != q.device):
+                raise ValueError("mha: bias_k / bias_v must be contiguous float32 [1, 1, E] on the query's device")
+        lnp = ln if ln else (None, None)
+        return _MHAFn.apply((heads, bool(causal), eps, p, bool(addq), bool(add_zero_attn)), q, kv, in_proj_weight,
+                            in_proj_bias, out_weight, out_bias, qpad, kpad, *lnp, bias_k, bias_v)
     if p == 0.0 and _one_key(q, kv):   # with dropout the single probability 1 is still dropped: _MHAFn
         return _MHAOneKeyFn.apply("add" if addq else eps, q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias,
                                   qpad, kpad, *ln)
@@ -346,25 +421,28 @@ def _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causa
 
 
 def mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal=False,
-        qpad=None, kpad=None, dropout_p=0.0):
+        qpad=None, kpad=None, dropout_p=0.0, bias_k=None, bias_v=None, add_zero_attn=False):
     """nn.MultiheadAttention(batch_first, kdim=vdim=E)(q, kv, kv) with the reference mask rules.
-    dropout_p > 0: dropout on the attention probabilities (the module's training mode)."""
-    return _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p)
+    dropout_p > 0: dropout on the attention probabilities (the module's training mode).
+    bias_k / bias_v, add_zero_attn: the module's add_bias_kv / add_zero_attn keys (see _mha)."""
+    return _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
+                bias_k=bias_k, bias_v=bias_v, add_zero_attn=add_zero_attn)
 
 
 def mha_residual_layernorm(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, gamma, beta,
-                           eps=1e-5, causal=False, qpad=None, kpad=None, dropout_p=0.0):
+                           eps=1e-5, causal=False, qpad=None, kpad=None, dropout_p=0.0, bias_k=None, bias_v=None,
+                           add_zero_attn=False):
     """LN(MHA(q, kv, kv) + q): ResidualConnection(MHAMixer) (mixer_block.py:567-603); the query
     projection's input-gradient GEMM takes the residual gradient in its epilogue."""
     return _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
-                float(eps), (gamma, beta))
+                float(eps), (gamma, beta), bias_k=bias_k, bias_v=bias_v, add_zero_attn=add_zero_attn)
 
 
 def mha_residual(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal=False,
-                 qpad=None, kpad=None, dropout_p=0.0):
+                 qpad=None, kpad=None, dropout_p=0.0, bias_k=None, bias_v=None, add_zero_attn=False):
     """MHA(q, kv, kv) + q: ResidualConnection(MHAMixer) without a LayerNorm.  q is added by the output
     projection's GEMM (epilogue 3) in both forms of mha, and the gradient of the sum by the query
     projection's input-gradient GEMM (the one-key form has no query projection: there dq is the
     gradient itself)."""
     return _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
-                addq=True)
+                addq=True, bias_k=bias_k, bias_v=bias_v, add_zero_attn=add_zero_attn)

@@ -275,7 +275,7 @@ def embedding_mixer_form(metaformer_block) -> Optional[Tuple[List[Tuple[str, lis
 
 def integrator_form(integrate_modal_block) -> Optional[IntegratorForm]:
     """IntegratorForm of an IntegrateModalBlock whose integrators are single-block cross-attention
-    layerds (no projections, one batch_first MHA without output nonlinearity or bias_k, residual LN,
+    layerds (no projections, one batch_first MHA without output nonlinearity or extra keys (bias_k, add_zero_attn), residual LN,
     one-Linear residual-LN FeedForward) of cat_linear's width, with one head count and one eps."""
     blk = integrate_modal_block
     n = len(blk.integrators)
@@ -295,7 +295,8 @@ def integrator_form(integrate_modal_block) -> Optional[IntegratorForm]:
             return None
         mha = res.module.mixer[0].mha
         if (not mha.batch_first or mha.in_proj_bias is None or tuple(mha.in_proj_weight.shape) != (3 * E, E)
-                or mha.out_proj.bias is None or getattr(mha, "bias_k", None) is not None):
+                or mha.out_proj.bias is None or getattr(mha, "bias_k", None) is not None
+                or getattr(mha, "add_zero_attn", False)):
             return None
         tail = _linear_residual_ln(integ.mixer[0].feed_forward)
         if tail is None:

@@ -296,8 +296,6 @@ class MultiheadAttention(nn.Module):
     def __init__(self, embed_dim, num_heads, dropout=0.0, bias=True, add_bias_kv=False,
                  add_zero_attn=False, kdim=None, vdim=None, batch_first=False, device=None, dtype=None):
         super().__init__()
-        if add_bias_kv or add_zero_attn:
-            _unsupported("MHA add_bias_kv / add_zero_attn")
         if (kdim not in (None, embed_dim)) or (vdim not in (None, embed_dim)):
             _unsupported("MHA kdim/vdim != embed_dim")
         if not bias:
@@ -310,6 +308,16 @@ class MultiheadAttention(nn.Module):
         self.out_proj = Linear(embed_dim, embed_dim, bias=True, device=device, dtype=dtype)
         nn.init.xavier_uniform_(self.in_proj_weight)
         nn.init.zeros_(self.out_proj.bias)
+        # add_bias_kv: one more key / value row every query sees; add_zero_attn: one more all-zero key and
+        # value per head (no parameters).  Key order [real keys, bias key, zero key], as torch appends them
+        self.add_zero_attn = bool(add_zero_attn)
+        if add_bias_kv:
+            self.bias_k = nn.Parameter(torch.empty(1, 1, embed_dim, device=device, dtype=dtype))
+            self.bias_v = nn.Parameter(torch.empty(1, 1, embed_dim, device=device, dtype=dtype))
+            nn.init.xavier_normal_(self.bias_k)
+            nn.init.xavier_normal_(self.bias_v)
+        else:
+            self.bias_k = self.bias_v = None
 
     def forward(self, query, key, value, key_padding_mask=None, need_weights=False, attn_mask=None,
                 average_attn_weights=False, is_causal=False):
@@ -326,7 +334,8 @@ class MultiheadAttention(nn.Module):
             causal, qpad, kpad = True, attn_mask.main_pad, attn_mask.other_pad
         out = Fn.mha(query, key, self.in_proj_weight, self.in_proj_bias, self.out_proj.weight,
                      self.out_proj.bias, self.num_heads, causal, qpad, kpad,
-                     dropout_p=self.dropout if self.training else 0.0)
+                     dropout_p=self.dropout if self.training else 0.0,
+                     bias_k=self.bias_k, bias_v=self.bias_v, add_zero_attn=self.add_zero_attn)
         if not self.batch_first:
             out = out.transpose(0, 1)
         return out, None

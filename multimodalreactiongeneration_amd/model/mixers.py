@@ -130,7 +130,8 @@ class MHAMixer(Mixer):
         mha, causal, qpad, kpad = form
         return Fn.mha_residual_layernorm(q, k, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
                                          mha.out_proj.bias, mha.num_heads, ln.weight, ln.bias, ln.eps,
-                                         causal, qpad, kpad, dropout_p=mha.dropout if mha.training else 0.0)
+                                         causal, qpad, kpad, dropout_p=mha.dropout if mha.training else 0.0,
+                                         bias_k=mha.bias_k, bias_v=mha.bias_v, add_zero_attn=mha.add_zero_attn)
 
     def fused_residual(self, q, k, v, attn_mask=None):
         """MHA(q, k, v) + q with q added by the output projection's GEMM (same forms as above)."""
@@ -140,7 +141,8 @@ class MHAMixer(Mixer):
         mha, causal, qpad, kpad = form
         return Fn.mha_residual(q, k, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
                                mha.out_proj.bias, mha.num_heads, causal, qpad, kpad,
-                               dropout_p=mha.dropout if mha.training else 0.0)
+                               dropout_p=mha.dropout if mha.training else 0.0,
+                               bias_k=mha.bias_k, bias_v=mha.bias_v, add_zero_attn=mha.add_zero_attn)
 
     def forward(self, q, k, v, attn_mask=None):
         if len(self.mixer) > 1:
