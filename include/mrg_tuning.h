@@ -18,6 +18,14 @@ extern "C" {
  * >= 2048 rows, >= 256 columns): ring depth 2..4 (0 = off; default 2, MRG_GEMM_GLDS) and column
  * tile (64 forces 64-wide tiles, 128 = by shape).                                               */
 int mrg_gemm_set_glds(int depth, int bn);
+/* The current ring depth and column tile of mrg_gemm_set_glds (host state; both outputs required). */
+int mrg_gemm_get_glds(int* depth, int* bn);
+/* Tests: the kernel family that the calling thread's most recent GEMM entry point launched for the
+ * product itself (reduce and row-sum passes do not count): "gemm_rows_kernel", "gemm_x6g_kernel",
+ * "gemm_x6g_wgrad_kernel", "gemm_x6w_kernel", or the generic tile kernels "gemm_x6_kernel:T" /
+ * "gemm_f32_kernel:T" with T the tile (0: 128x128, 1: 128x64, 2: 64x64) and "+cnt" appended when the
+ * in-launch split-K combine was armed.  "" before the first launch.  Host state, a string literal. */
+const char* mrg_gemm_last_kernel(void);
 /* Weight-gradient products (transA 1, transB 0) on the LDS-DMA kernel (1, default) or the
  * register-staged one (0); returns the previous setting.                                        */
 int mrg_gemm_set_glds_wg(int on);

@@ -38,6 +38,8 @@ SIGNATURES = {
     "mrg_gemm_set_blocks_per_cu": (c_int, [c_int]),
     "mrg_attention_set_fused": (c_int, [c_int]),
     "mrg_gemm_set_glds": (c_int, [c_int, c_int]),
+    "mrg_gemm_get_glds": (c_int, [PI, PI]),
+    "mrg_gemm_last_kernel": (ctypes.c_char_p, []),
     "mrg_gemm_set_glds_wg": (c_int, [c_int]),
     "mrg_transpose_batched": (c_int, [c_int, PP, PP, PI, PI, P]),
     "mrg_split_planes_batched": (c_int, [c_int, PP, PP, PI, PI, PI, P]),

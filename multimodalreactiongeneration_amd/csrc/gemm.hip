@@ -922,10 +922,27 @@ static int launch_gemm(int mode, const GemmArgs& a, int tile, int bk, int ta, in
   return 0;
 }
 
+// name of the generic tiled launch: the kernel that ran (x6 split / bf16 operands, or exact f32),
+// its tile (0: 128x128, 1: 128x64, 2: 64x64) and "+cnt" when the in-launch split-K combine is armed
+static const char* tile_kernel_name(bool mx, int tile, bool cnt) {
+  static const char* const f32[3] = {"gemm_f32_kernel:0", "gemm_f32_kernel:1", "gemm_f32_kernel:2"};
+  static const char* const x6[2][3] = {{"gemm_x6_kernel:0", "gemm_x6_kernel:1", "gemm_x6_kernel:2"},
+                                       {"gemm_x6_kernel:0+cnt", "gemm_x6_kernel:1+cnt", "gemm_x6_kernel:2+cnt"}};
+  tile = tile < 0 ? 0 : (tile > 2 ? 2 : tile);
+  return mx ? x6[cnt ? 1 : 0][tile] : f32[tile];
+}
+
 MRG_EPI_NS_END
+#if !MRG_SMOOTH_EPI
+thread_local const char* g_last_gemm_kernel = "";
+#endif
 }  // namespace mrg
 
 using namespace mrg;
+
+#if !MRG_SMOOTH_EPI
+MRG_API const char* mrg_gemm_last_kernel(void) { return g_last_gemm_kernel; }
+#endif
 
 // GEMM arithmetic mode: 1 = fp32 via the x6 bf16 split (default), 0 = exact f32 MFMA
 // (v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain).  Env MRG_GEMM_EXACT=1 selects 0 at load.
@@ -950,6 +967,12 @@ MRG_API int mrg_gemm_set_glds(int depth, int bn) {
   MRG_REQUIRE(bn == 64 || bn == 128, "mrg_gemm_set_glds: column tile must be 64 or 128");
   g_glds = depth;
   g_glds_bn = bn;
+  return 0;
+}
+MRG_API int mrg_gemm_get_glds(int* depth, int* bn) {
+  MRG_REQUIRE(depth && bn, "mrg_gemm_get_glds: null output");
+  *depth = g_glds;
+  *bn = g_glds_bn;
   return 0;
 }
 
@@ -1086,6 +1109,7 @@ static int gemm_ex(int mode, int M, int N, int K, float alpha,
     a.a_bytes = (int)(a_ext * 4);
     a.b_bytes = (int)(b_ext * 4);
     launch_rows(a, stream);
+    g_last_gemm_kernel = "gemm_rows_kernel";
     return check_launch("gemm_rows_kernel");
   }
   // LDS-DMA pipelined x6 kernel: k-contiguous A and B, whole 32-deep k-tiles, unsplit
@@ -1099,6 +1123,7 @@ static int gemm_ex(int mode, int M, int N, int K, float alpha,
     else if (N == 256 && K <= 256) bn = 64;
     if (g_glds_bn == 64) bn = 64;
     launch_x6g(a, g_glds, bm, bn, stream, mode == 2 ? 1 : 3);
+    g_last_gemm_kernel = "gemm_x6g_kernel";
     return check_launch("gemm_x6g_kernel");
   }
   int tile;  // 0: 128x128, 1: 128x64, 2: 64x64
@@ -1129,14 +1154,17 @@ static int gemm_ex(int mode, int M, int N, int K, float alpha,
   // weight gradients (dY^T X) on the LDS-DMA kernel: k-strided operands, split-K slabs, fused row sums
   const bool wg = mx && g_glds_wg && g_tile_override < 0 && transA && !transB && va && vb && K > 0 &&
                   (K % 32) == 0 && (M % 4) == 0 && (N % 4) == 0 && M >= 64 && N >= 64 && !a.cnt;
+  const char* kname = "gemm_x6g_wgrad_kernel";
   if (wg) {
     tile = 0;
     const int cap = g_blocks_per_cu > 0 ? g_blocks_per_cu * resident_cus() : 0;
     launch_x6g_wgrad(a, splits, 128, 128, stream, mode == 2 ? 1 : 3, cap);
-  } else if (launch_gemm(mode, a, tile, bk, transA, transB, va, vb, splits, stream)) {
-    return 2;
+  } else {
+    kname = tile_kernel_name(mx, tile, a.cnt != nullptr);
+    if (launch_gemm(mode, a, tile, bk, transA, transB, va, vb, splits, stream)) return 2;
   }
-  if (check_launch("gemm_f32_kernel")) return 1;
+  g_last_gemm_kernel = kname;
+  if (check_launch(kname)) return 1;
   // unsplit 64x64-tile GEMM (x6): its n0 == 0 tiles wrote asum_out directly
   bool asum_done = splits == 1 && tile == 2 && mx;
   if (splits > 1 && !a.cnt) {
@@ -1248,6 +1276,7 @@ MRG_API int mrg_gemm_x6g_batched(int n, int M, int N, int K, float alpha, const 
   else if (N == 256 && K <= 256) bn = 64;
   if (g_glds_bn == 64) bn = 64;
   launch_x6g(a, g_glds, bm, bn, stream, mode == 2 ? 1 : 3, &gb);
+  g_last_gemm_kernel = "gemm_x6g_kernel";
   return check_launch("gemm_x6g_kernel (batched)");
 }
 

@@ -42,6 +42,12 @@ int x6_planes_batched(int n, int M, int N, int K, float alpha, const float* cons
                       const float* const* bias, int epilogue, const float* const* aux, long ldaux,
                       hipStream_t stream);
 }  // namespace smooth_entry
+
+// Kernel family the calling thread's most recent GEMM entry point launched for the product itself
+// (mrg_gemm_last_kernel: a string literal, stored at the launch sites; defined once, in gemm.hip's
+// default build)
+extern thread_local const char* g_last_gemm_kernel;
+
 MRG_EPI_NS_BEGIN
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -777,6 +777,7 @@ MRG_API int mrg_gemm_x6_planes(int M, int N, int K, float alpha, const float* A,
   if (g_wide_cfg > 8) {   // row-owning kernel (gemm_wide.hip); cfg = 10 * bn / 64 + ns, 0 = the kernel below
     const int bn = N <= 64 ? 64 : 64 * (g_wide_cfg / 10), ns = g_wide_cfg % 10;
     launch_x6w(a, bn, ns, bplane, stream);
+    g_last_gemm_kernel = "gemm_x6w_kernel";
     return check_launch("gemm_x6w_kernel");
   }
   int bm = 64, bn = 128;  // the fp32-operand kernel's shape rule (gemm.hip)
@@ -785,6 +786,7 @@ MRG_API int mrg_gemm_x6_planes(int M, int N, int K, float alpha, const float* A,
   GemmBatch none;
   none.n = 0;
   launch_shape<1>(a, 2, bm, bn, bplane, stream, none);
+  g_last_gemm_kernel = "gemm_x6g_kernel";
   return check_launch("gemm_x6g_kernel");
 }
 
@@ -828,6 +830,7 @@ MRG_API int mrg_gemm_x6_planes_batched(int n, int M, int N, int K, float alpha, 
   a.vec = vec;
   const int cfg = g_wide_cfg > 8 ? g_wide_cfg : 12;
   launch_x6w(a, N <= 64 ? 64 : 64 * (cfg / 10), cfg % 10, bplane, stream, &gb);
+  g_last_gemm_kernel = "gemm_x6w_kernel";
   return check_launch("gemm_x6w_kernel (batched)");
 }
 

@@ -21,12 +21,40 @@ DEV = "cuda:0"
 
 @pytest.fixture(scope="module", autouse=True)
 def _lib():
+    """Loads the library; at teardown every process-wide GEMM and LSTM knob is as the module found it
+    (GEMM mode, glds depth / bn, glds_wg, wide, blocks_per_cu, forced tile, LSTM mx / solo), so no test
+    here changes the kernels that the later tests and files run.  Knobs with neither a getter nor a
+    setter that returns the old value (mrg_lstm_config, mrg_lstm_set_local_handoff, the min_bs
+    threshold of mrg_lstm_set_mx) are left out; the forced tile, which has no read-back either, is read
+    off mrg_gemm_last_kernel after two tiny products (gemm_ref.probe_forced_tile)."""
     from multimodalreactiongeneration_amd import _lib as L
-    L.load()
+    from tests import gemm_ref
+    lib = L.load()
+    before = gemm_ref.read_knobs(lib, lambda: gemm_ref.probe_forced_tile(lib, _tiny_gemm))
     yield
     from multimodalreactiongeneration_amd import functional as Fn
     torch.cuda.synchronize()
     Fn.check_errors()
+    after = gemm_ref.read_knobs(lib, lambda: gemm_ref.probe_forced_tile(lib, _tiny_gemm))
+    for knob in before:
+        assert after[knob] == before[knob], f"a test left the process-wide knob '{knob}' at {after[knob]} " \
+                                            f"(the module found {before[knob]})"
+
+
+def _tiny_gemm(ta, M, N, K, splits):
+    """one small all-zero product through mrg_gemm_f32_ex (the forced-tile probe's launches)"""
+    import ctypes
+    from multimodalreactiongeneration_amd import _lib as L
+    lib = L.load()
+    a = torch.zeros((K, M) if ta else (M, K), device=DEV)
+    b = torch.zeros(K, N, device=DEV)
+    c = torch.zeros(M, N, device=DEV)
+    ws = torch.zeros(max(1, lib.mrg_gemm_workspace_bytes(M, N, splits) // 4), device=DEV)
+    VP = ctypes.c_void_p
+    L.check(lib.mrg_gemm_f32_ex(M, N, K, 1.0, VP(a.data_ptr()), ta, M if ta else K, 0, 0, VP(b.data_ptr()), 0, N, 0, 0,
+                                0.0, VP(c.data_ptr()), N, None, 0, None, 0, VP(ws.data_ptr()), splits, None, None, 0.0,
+                                None, VP(torch.cuda.current_stream().cuda_stream)), "probe")
+    torch.cuda.synchronize()
 
 
 def _param(t):
@@ -103,16 +131,24 @@ def test_few_row_gemms(M, N, K, epi, split):
 
 @pytest.mark.parametrize("depth,bn", [(2, 128), (3, 128), (3, 64), (4, 128)])
 @pytest.mark.parametrize("M,N,K,epi,rowmap", [
-    (19200, 1024, 256, 0, False), (19200, 256, 256, 3, False), (1000, 192, 96, 1, False), (300, 64, 32, 0, False),
+    (19200, 1024, 256, 0, False), (19200, 256, 256, 3, False), (2049, 260, 96, 1, False), (2100, 257, 32, 0, False),
     (64 * 300, 256, 512, 0, True)])
 def test_glds_gemm_vs_fp64(M, N, K, epi, rowmap, depth, bn):
     """The LDS-DMA pipelined x6 kernel (gemm_x6g_kernel: k-contiguous A and B, DMA ring of `depth`
     k-tiles, fragments split into bf16 planes as they are read) against fp64: M and N edges
-    (clamped rows, masked stores), bias / beta / ReLU / residual epilogues, and an A read through a
-    RowMap ([B, T] rows of a [B, T + 12, K] view: the [:, lead:] slice).  Bitwise repeatable."""
+    (2049 x 260: one clamped row in the last M tile, N past a tile edge; 2100 x 257 with ldc = 257: the
+    scalar store path, and one k-tile, fewer than any ring depth), bias / beta / ReLU / residual
+    epilogues, and an A read through a RowMap ([B, T] rows of a [B, T + 12, K] view: the [:, lead:]
+    slice).  Bitwise repeatable; every case asserts that gemm_x6g_kernel is what ran, and the ring depth
+    and column tile are put back as found."""
+    import ctypes
     from multimodalreactiongeneration_amd import functional as Fn
     from multimodalreactiongeneration_amd import _lib as L
     lib = L.load()
+    d0, bn0 = ctypes.c_int(), ctypes.c_int()
+    L.check(lib.mrg_gemm_get_glds(ctypes.byref(d0), ctypes.byref(bn0)), "get glds")
+    mode0 = lib.mrg_gemm_get_mode()
+    L.check(lib.mrg_gemm_set_mode(1), "mode")
     g = torch.Generator().manual_seed(M + 7 * N + K + depth)
     if rowmap:
         B_, T_ = 64, M // 64
@@ -136,10 +172,12 @@ def test_glds_gemm_vs_fp64(M, N, K, epi, rowmap, depth, bn):
             c = c0.to(DEV)
             Fn.gemm(M, N, K, a_ptr, 0, lda, Fn._ptr(wd), 1, K, Fn._ptr(c), N, beta=0.5, bias=Fn._ptr(bd), epi=epi,
                     aux=Fn._ptr(auxd) if epi >= 2 else None, ldaux=N, a_hi=a_hi, a_div=a_div, device=DEV)
+            assert lib.mrg_gemm_last_kernel() == b"gemm_x6g_kernel"
             outs.append(c)
         torch.cuda.synchronize()
     finally:
-        L.check(lib.mrg_gemm_set_glds(0, 128), "glds")
+        L.check(lib.mrg_gemm_set_glds(d0.value, bn0.value), "glds")
+        L.check(lib.mrg_gemm_set_mode(mode0), "mode")
     ref = a.double() @ w.double().t() + 0.5 * c0.double() + bias.double()
     if epi == 1:
         ref = ref.clamp_min(0)
@@ -1191,6 +1229,10 @@ def test_batched_gemm_matches_single_products(M, N, K, epi, n, gemm_mode):
     arr = lambda v: (VP * n)(*[VP(t.data_ptr()) for t in v])  # noqa: E731
     L.check(lib.mrg_gemm_x6g_batched(n, M, N, K, 1.0, arr(As), K, arr(Ws), K, 0.0, arr(Cs), N, arr(bs), epi,
                                      None if aux is None else arr(aux), N, 0, Fn._stream()), "batched")
+    # the LDS-DMA kernel takes the shapes inside its gate in x6 mode (one launch for all n problems);
+    # everything else is the documented loop of single products
+    glds = M >= 2048 and N >= 256 and K % 32 == 0 and gemm_mode == 1
+    assert (lib.mrg_gemm_last_kernel() == b"gemm_x6g_kernel") == glds, lib.mrg_gemm_last_kernel()
     for i in range(n):
         ref = torch.empty(M, N, device=DEV)
         L.check(lib.mrg_gemm_f32_ex(M, N, K, 1.0, VP(As[i].data_ptr()), 0, K, 0, 0, VP(Ws[i].data_ptr()), 1, K, 0, 0,
