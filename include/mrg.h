@@ -490,6 +490,34 @@ int mrg_attention_extra_bwd(int B, int heads, int Tq, int D, const float* q, lon
                             const float* pk, long pk_bs, long pk_ts, const float* lse_main, float* cbuf,
                             float* workspace, hipStream_t stream);
 
+/* nn.MultiheadAttention(need_weights=True): the attention probabilities, rebuilt from the projected
+ * q / k (element layout of mrg_attention_fwd, D in {8, 16, 32, 64}, K rows 16-B aligned) and the
+ * [B, heads, Tq] log-sum-exp over every visible key that mrg_attention_fwd(_dropout) left, after
+ * mrg_attention_extra_fwd where there are extra keys (csrc/attention_weights.hip).  Nothing of score
+ * size exists unless this is called.  Columns: Tk + n in torch's order [real keys, bias key, zero key];
+ * bias_k [heads * D] nullable, zero_attn a flag.
+ *   P[b, h, i, j] = exp(scale q.k - lse) where the block-causal / padding-AND rules admit (i, j) and
+ *   exactly 0.0f where they hide it; the extra columns, always visible, exp(scale q.bias_k - lse) and
+ *   exp(-lse); a row whose lse is NaN (fully hidden, no extra key) is NaN in every column.
+ *   lse is the row's log-sum-exp rounded to one float32, and that rounding would scale a whole row, so
+ *   each row is divided by the sum of its own terms taken in double (1 up to that rounding): rows sum
+ *   to 1 to the last float32 rounding.  For this every workgroup sums its rows over all column tiles
+ *   first: the score products are formed Tk / 64 times in all.
+ * key nullable: with it the result is P o keep * scale_keep, element (b * heads + head, q, column) of
+ * the attention index map over Tk + n columns (mrg_attention_keep_mask's mask): the weights o was built
+ * from.  average = 0: out [B, heads, Tq, Tk + n]; average != 0: out [B, Tq, Tk + n], the mean over the
+ * heads summed in head order inside one workgroup (no atomics: bitwise reproducible).  The score tiles
+ * are the forward's (same MFMA chain and operand order).  Rows are stored contiguously, 16 bytes at a
+ * time where the address allows, scalars otherwise (any Tk + n, any out alignment of 4 bytes).
+ * Tq and B * heads at most 65535.  The kernel is one store of 4 bytes per score and the row-sum pass;
+ * its rate has not been measured.                                                                    */
+int mrg_attention_weights(int B, int heads, int Tq, int Tk, int D,
+                          const float* q, long q_bs, long q_ts, const float* k, long k_bs, long k_ts,
+                          const float* bias_k, int zero_attn, const float* lse,
+                          const unsigned char* qpad, const unsigned char* kpad, int causal, float scale,
+                          int average, unsigned int thr, float scale_keep, const unsigned long long* key,
+                          float* out, hipStream_t stream);
+
 /* ---------------------------------------------------------------- LayerNorm
  * y = LayerNorm(a + b) (ResidualConnection.forward, residual_connection.py:
  * 20-37), rows x E, 1 <= E <= 1024; mean/rstd saved per row.     */

@@ -129,6 +129,8 @@ SIGNATURES = {
                                           P, c_long, c_long, P, c_uint, c_float, P, P]),
     "mrg_attention_extra_fwd": (c_int, [c_int, c_int, c_int, c_int, P, c_long, c_long, P, P, c_int, c_float,
                                         P, c_long, c_long, P, c_int, c_uint, c_float, P, P]),
+    "mrg_attention_weights": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_long, c_long, P, c_long, c_long,
+                                      P, c_int, P, P, P, c_int, c_float, c_int, c_uint, c_float, P, P, P]),
     "mrg_attention_extra_bwd_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int]),
     "mrg_attention_extra_bwd": (c_int, [c_int, c_int, c_int, c_int, P, c_long, c_long, P, P, c_float,
                                         P, c_long, c_long, P, P, c_long, c_long, P, c_long, c_long,

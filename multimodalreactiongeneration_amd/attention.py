@@ -159,6 +159,9 @@ class _MHAFn(Function):
         # extra always-visible keys (add_bias_kv: bias_k / bias_v; add_zero_attn: rest[2]): one merge launch
         # after the attention kernel (_extra_fwd)
         zero_attn = bool(rest[2]) if len(rest) > 2 else False
+        # need_weights (rest[3]: None, "mean" or "heads"): a second, non-differentiable output, the attention
+        # probabilities rebuilt from Q, K and lse by one more launch (_weights)
+        want = rest[3] if len(rest) > 3 else None
         _lib.require_device(q_in)
         dev = q_in.device
         B, Tq, E = q_in.shape
@@ -207,11 +210,15 @@ class _MHAFn(Function):
         ctx.spec = (heads, causal, scale, eps is not None)
         ctx.addq = addq
         ctx.drop = drop
-        return res
+        if want is None:
+            return res
+        wts = _weights(heads, Q, KV, bias_k, zero_attn, lse, qpad, kpad, causal, scale, want == "mean", drop)
+        ctx.mark_non_differentiable(wts)
+        return res, wts
 
     @staticmethod
     @_keeps_precision
-    def backward(ctx, dout):
+    def backward(ctx, dout, _dweights=None):
         saved = ctx.saved_tensors
         q2, kv2, Q, KV, O, lse, in_w, in_b, out_w, out_b, qpad, kpad = saved[:12]
         heads, causal, scale, resln = ctx.spec
@@ -271,6 +278,36 @@ def _extra_fwd(heads, Q, bias_k, bias_v, zero_attn, scale, O, lse, Tk, drop):
     _lib.check(_lib.load().mrg_attention_extra_fwd(
         B, heads, Tq, E // heads, _ptr(Q), Tq * E, E, _ptr(bias_k), _ptr(bias_v), int(zero_attn), scale,
         _ptr(O), Tq * E, E, _ptr(lse), Tk, thr, sk, _ptr(key), _stream()), "attention extra keys fwd")
+
+
+def _weights(heads, Q, KV, bias_k, zero_attn, lse, qpad, kpad, causal, scale, average, drop):
+    """The attention probabilities of an op that holds the projected Q / KV, the (merged) lse and, with
+    dropout, the draw's key: [B, Tq, Tk + n] averaged over the heads or [B, heads, Tq, Tk + n], columns in
+    torch's order [real keys, bias key, zero key] (mrg_attention_weights: one launch, its throughput
+    not measured).  With dropout they are the dropped, rescaled ones O was built from, as torch's are."""
+    B, Tq, E = Q.shape
+    Tk = KV.shape[1]
+    W = Tk + (bias_k is not None) + bool(zero_attn)
+    shape = (B, Tq, W) if average else (B, heads, Tq, W)
+    out = torch.empty(*shape, device=Q.device, dtype=torch.float32)
+    thr, sk, key = drop if drop is not None else (0, 1.0, None)
+    _lib.check(_lib.load().mrg_attention_weights(
+        B, heads, Tq, Tk, E // heads, _ptr(Q), Tq * E, E, _ptr(KV), Tk * 2 * E, 2 * E, _ptr(bias_k),
+        int(bool(zero_attn)), _ptr(lse), _ptr(qpad), _ptr(kpad), int(causal), scale, int(bool(average)), thr, sk,
+        _ptr(key), _ptr(out), _stream()), "attention weights")
+    return out
+
+
+def _one_key_weights(q, heads, qpad, kpad, average):
+    """Weights of the one-key form: the softmax over a single visible key is 1, and NaN where the
+    pair is hidden (query AND key padding); there is no softmax to rebuild, so no kernel."""
+    B = q.shape[0]
+    shape = (B, 1, 1) if average else (B, heads, 1, 1)
+    w = torch.ones(*shape, device=q.device, dtype=torch.float32)
+    if qpad is not None and kpad is not None:
+        hide = (qpad.reshape(B, 1) & kpad.reshape(B, 1)).bool().view(B, *([1] * (len(shape) - 1)))
+        w = torch.where(hide, torch.full_like(w, float("nan")), w)
+    return w
 
 
 def _extra_bwd(heads, Q, KV, O, lse, qpad, kpad, causal, scale, bias_kv, dO, dQ, dKV, drop):
@@ -391,17 +428,23 @@ def _one_key(q, kv):
 
 
 def _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
-         eps=None, ln=(), addq=False, bias_k=None, bias_v=None, add_zero_attn=False):
+         eps=None, ln=(), addq=False, bias_k=None, bias_v=None, add_zero_attn=False, need_weights=False,
+         average_attn_weights=True):
     """The attention Function for these shapes; eps not None: LN(. + q) with ln = (gamma, beta); addq:
     . + q without a LayerNorm.  bias_k / bias_v ([1, 1, E] or [E]; both or neither) and add_zero_attn:
     nn.MultiheadAttention's extra keys, visible to every query whatever the mask rules say.  With one the
     call is always the unchunked _MHAFn: the one-key form does not apply (there is more than one key),
     and the query-chunked schedules (encoder_stack, integrate) never see such a module
-    (forms.integrator_form declines it), so the merge has no chunk form."""
+    (forms.integrator_form declines it), so the merge has no chunk form.
+    need_weights: return (out, weights), weights [B, Tq, Tk + n] (average_attn_weights) or
+    [B, heads, Tq, Tk + n] as nn.MultiheadAttention returns them, rebuilt by one more launch from what the
+    op holds (_weights).  They carry no gradient (requires_grad False: unlike torch, nothing trains through
+    them); out and its backward are the op's without them, launch for launch and draw for draw."""
     if in_proj_weight.shape[0] != 3 * q.shape[-1]:
         raise ValueError("in_proj_weight must be [3E, E]")
     p = float(dropout_p)
     _drop_consts(p)
+    want = ("mean" if average_attn_weights else "heads") if need_weights else None
     if (bias_k is None) != (bias_v is None):
         raise ValueError("mha: bias_k and bias_v come together")
     if bias_k is not None or add_zero_attn:
@@ -411,38 +454,46 @@ def _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causa
                                   or t.device != q.device):
                 raise ValueError("mha: bias_k / bias_v must be contiguous float32 [1, 1, E] on the query's device")
         lnp = ln if ln else (None, None)
-        return _MHAFn.apply((heads, bool(causal), eps, p, bool(addq), bool(add_zero_attn)), q, kv, in_proj_weight,
-                            in_proj_bias, out_weight, out_bias, qpad, kpad, *lnp, bias_k, bias_v)
+        spec = (heads, bool(causal), eps, p, bool(addq), bool(add_zero_attn)) + ((want,) if want else ())
+        return _MHAFn.apply(spec, q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, qpad, kpad, *lnp,
+                            bias_k, bias_v)
     if p == 0.0 and _one_key(q, kv):   # with dropout the single probability 1 is still dropped: _MHAFn
-        return _MHAOneKeyFn.apply("add" if addq else eps, q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias,
-                                  qpad, kpad, *ln)
-    return _MHAFn.apply((heads, bool(causal), eps, p, bool(addq)), q, kv, in_proj_weight, in_proj_bias, out_weight,
-                        out_bias, qpad, kpad, *ln)
+        out = _MHAOneKeyFn.apply("add" if addq else eps, q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias,
+                                 qpad, kpad, *ln)
+        return (out, _one_key_weights(q, heads, qpad, kpad, want == "mean")) if want else out
+    spec = (heads, bool(causal), eps, p, bool(addq)) + ((False, want) if want else ())
+    return _MHAFn.apply(spec, q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, qpad, kpad, *ln)
 
 
 def mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal=False,
-        qpad=None, kpad=None, dropout_p=0.0, bias_k=None, bias_v=None, add_zero_attn=False):
+        qpad=None, kpad=None, dropout_p=0.0, bias_k=None, bias_v=None, add_zero_attn=False,
+        need_weights=False, average_attn_weights=True):
     """nn.MultiheadAttention(batch_first, kdim=vdim=E)(q, kv, kv) with the reference mask rules.
     dropout_p > 0: dropout on the attention probabilities (the module's training mode).
-    bias_k / bias_v, add_zero_attn: the module's add_bias_kv / add_zero_attn keys (see _mha)."""
+    bias_k / bias_v, add_zero_attn: the module's add_bias_kv / add_zero_attn keys (see _mha).
+    need_weights: (out, weights) with the attention probabilities, no gradient through them (see _mha)."""
     return _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
-                bias_k=bias_k, bias_v=bias_v, add_zero_attn=add_zero_attn)
+                bias_k=bias_k, bias_v=bias_v, add_zero_attn=add_zero_attn, need_weights=need_weights,
+                average_attn_weights=average_attn_weights)
 
 
 def mha_residual_layernorm(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, gamma, beta,
                            eps=1e-5, causal=False, qpad=None, kpad=None, dropout_p=0.0, bias_k=None, bias_v=None,
-                           add_zero_attn=False):
+                           add_zero_attn=False, need_weights=False, average_attn_weights=True):
     """LN(MHA(q, kv, kv) + q): ResidualConnection(MHAMixer) (mixer_block.py:567-603); the query
     projection's input-gradient GEMM takes the residual gradient in its epilogue."""
     return _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
-                float(eps), (gamma, beta), bias_k=bias_k, bias_v=bias_v, add_zero_attn=add_zero_attn)
+                float(eps), (gamma, beta), bias_k=bias_k, bias_v=bias_v, add_zero_attn=add_zero_attn,
+                need_weights=need_weights, average_attn_weights=average_attn_weights)
 
 
 def mha_residual(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal=False,
-                 qpad=None, kpad=None, dropout_p=0.0, bias_k=None, bias_v=None, add_zero_attn=False):
+                 qpad=None, kpad=None, dropout_p=0.0, bias_k=None, bias_v=None, add_zero_attn=False,
+                 need_weights=False, average_attn_weights=True):
     """MHA(q, kv, kv) + q: ResidualConnection(MHAMixer) without a LayerNorm.  q is added by the output
     projection's GEMM (epilogue 3) in both forms of mha, and the gradient of the sum by the query
     projection's input-gradient GEMM (the one-key form has no query projection: there dq is the
     gradient itself)."""
     return _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
-                addq=True, bias_k=bias_k, bias_v=bias_v, add_zero_attn=add_zero_attn)
+                addq=True, bias_k=bias_k, bias_v=bias_v, add_zero_attn=add_zero_attn, need_weights=need_weights,
+                average_attn_weights=average_attn_weights)

@@ -351,12 +351,20 @@ def _dropout_active(module) -> bool:
     return False
 
 
+def _records_attention(module) -> bool:
+    """An attention of the module keeps its weights (MultiheadAttention.record_weights): the fused
+    frames would bypass it."""
+    from .model.layers import MultiheadAttention
+    return any(isinstance(m, MultiheadAttention) and m.record_weights is not None for m in module.modules())
+
+
 def plan_for(model) -> Optional[GenPlan]:
     """The model's GenPlan (cached per module identity and parameter storage), or None outside it.
-    Eligibility is cached, so the one thing that changes with model.train() / eval() is re-checked on
-    every call: with an active dropout the frames take the module path, as the reference's would."""
+    Eligibility is cached, so what changes after construction is re-checked on every call: with an
+    active dropout (model.train() / eval()) the frames take the module path, as the reference's would,
+    and so they do while an attention records its weights (the switch is never part of the plan)."""
     mf = model.metaformer
-    if _dropout_active(mf):
+    if _dropout_active(mf) or _records_attention(mf):
         return None
     key = (id(mf), mf.feature_embedding[0].weight.data_ptr(), model.ratio)
     p = _PLANS.get(key)

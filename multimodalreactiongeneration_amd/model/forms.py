@@ -298,6 +298,9 @@ def integrator_form(integrate_modal_block) -> Optional[IntegratorForm]:
                 or mha.out_proj.bias is None or getattr(mha, "bias_k", None) is not None
                 or getattr(mha, "add_zero_attn", False)):
             return None
+        if getattr(mha, "record_weights", None) is not None:   # a recording attention runs as a module (its
+            return None                                        # weights are kept there); read on every call
+
         tail = _linear_residual_ln(integ.mixer[0].feed_forward)
         if tail is None:
             return None

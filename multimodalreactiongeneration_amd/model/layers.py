@@ -319,12 +319,57 @@ class MultiheadAttention(nn.Module):
         else:
             self.bias_k = self.bias_v = None
 
+    # attention maps for analysis: None, "mean" (head average, [B, Tq, Tk + n]) or "heads"
+    # ([B, heads, Tq, Tk + n]).  When set, every call through this module (forward, or a fused residual
+    # route of its mixer) leaves the detached weights in last_weights, and the fused schedules that would
+    # bypass the module decline the model (forms.integrator_form, generate.plan_for).  Plain attributes:
+    # neither enters state_dict().
+    RECORD_MODES = (None, "mean", "heads")
+
+    @property
+    def record_weights(self):
+        return self.__dict__.get("_record_weights")
+
+    @record_weights.setter
+    def record_weights(self, mode):
+        if mode not in self.RECORD_MODES:
+            raise ValueError(f"record_weights must be None, 'mean' or 'heads', got {mode!r}")
+        self.__dict__["_record_weights"] = mode
+
+    @property
+    def last_weights(self):
+        return self.__dict__.get("_last_weights")
+
+    @last_weights.setter
+    def last_weights(self, w):
+        self.__dict__["_last_weights"] = w
+
+    def attend(self, op, *args, need_weights=False, average_attn_weights=True, **kw):
+        """op(*args, ...) for one of functional.mha / mha_residual_layernorm / mha_residual with this
+        module's recording applied: the weights are asked for when the caller or record_weights wants
+        them, kept in last_weights when recording, and (out, weights or None) is returned.  The switch is
+        read on every call."""
+        rec = self.record_weights
+        if not need_weights and rec is None:
+            return op(*args, **kw), None
+        if not need_weights or rec is None or (rec == "mean") == bool(average_attn_weights):
+            # one form serves: the caller's, or the recorder's when the caller asks for nothing
+            average = bool(average_attn_weights) if need_weights else rec == "mean"
+            out, w = op(*args, need_weights=True, average_attn_weights=average, **kw)
+            if rec is not None:
+                self.last_weights = w.detach()
+            return out, (w if need_weights else None)
+        # the caller and the recorder want different forms: the per-head map serves both
+        out, w = op(*args, need_weights=True, average_attn_weights=False, **kw)
+        self.last_weights = w.detach().mean(dim=1) if rec == "mean" else w.detach()
+        return out, (w.mean(dim=1) if average_attn_weights else w)
+
     def forward(self, query, key, value, key_padding_mask=None, need_weights=False, attn_mask=None,
-                average_attn_weights=False, is_causal=False):
+                average_attn_weights=True, is_causal=False):
         if key is not value:
             _unsupported("MHA with distinct key and value tensors")
-        if key_padding_mask is not None or need_weights:
-            _unsupported("MHA key_padding_mask / need_weights")
+        if key_padding_mask is not None:
+            _unsupported("MHA key_padding_mask (padding comes with masks.gen_attention_mask)")
         if not self.batch_first:
             query, key = query.transpose(0, 1), key.transpose(0, 1)
         causal, qpad, kpad = False, None, None
@@ -332,13 +377,14 @@ class MultiheadAttention(nn.Module):
             if not isinstance(attn_mask, BlockCausalMask):
                 _unsupported("dense attn_mask (use masks.gen_attention_mask)")
             causal, qpad, kpad = True, attn_mask.main_pad, attn_mask.other_pad
-        out = Fn.mha(query, key, self.in_proj_weight, self.in_proj_bias, self.out_proj.weight,
-                     self.out_proj.bias, self.num_heads, causal, qpad, kpad,
-                     dropout_p=self.dropout if self.training else 0.0,
-                     bias_k=self.bias_k, bias_v=self.bias_v, add_zero_attn=self.add_zero_attn)
+        out, weights = self.attend(Fn.mha, query, key, self.in_proj_weight, self.in_proj_bias, self.out_proj.weight,
+                                   self.out_proj.bias, self.num_heads, causal, qpad, kpad,
+                                   dropout_p=self.dropout if self.training else 0.0,
+                                   bias_k=self.bias_k, bias_v=self.bias_v, add_zero_attn=self.add_zero_attn,
+                                   need_weights=need_weights, average_attn_weights=average_attn_weights)
         if not self.batch_first:
             out = out.transpose(0, 1)
-        return out, None
+        return out, weights
 
 
 class MHAforSequentail(nn.Module):

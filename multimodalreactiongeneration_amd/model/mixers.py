@@ -128,10 +128,11 @@ class MHAMixer(Mixer):
         if form is None:
             return None
         mha, causal, qpad, kpad = form
-        return Fn.mha_residual_layernorm(q, k, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
-                                         mha.out_proj.bias, mha.num_heads, ln.weight, ln.bias, ln.eps,
-                                         causal, qpad, kpad, dropout_p=mha.dropout if mha.training else 0.0,
-                                         bias_k=mha.bias_k, bias_v=mha.bias_v, add_zero_attn=mha.add_zero_attn)
+        # through the module's attend: a recording attention keeps its weights on this route too
+        return mha.attend(Fn.mha_residual_layernorm, q, k, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
+                          mha.out_proj.bias, mha.num_heads, ln.weight, ln.bias, ln.eps,
+                          causal, qpad, kpad, dropout_p=mha.dropout if mha.training else 0.0,
+                          bias_k=mha.bias_k, bias_v=mha.bias_v, add_zero_attn=mha.add_zero_attn)[0]
 
     def fused_residual(self, q, k, v, attn_mask=None):
         """MHA(q, k, v) + q with q added by the output projection's GEMM (same forms as above)."""
@@ -139,10 +140,10 @@ class MHAMixer(Mixer):
         if form is None:
             return None
         mha, causal, qpad, kpad = form
-        return Fn.mha_residual(q, k, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
-                               mha.out_proj.bias, mha.num_heads, causal, qpad, kpad,
-                               dropout_p=mha.dropout if mha.training else 0.0,
-                               bias_k=mha.bias_k, bias_v=mha.bias_v, add_zero_attn=mha.add_zero_attn)
+        return mha.attend(Fn.mha_residual, q, k, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
+                          mha.out_proj.bias, mha.num_heads, causal, qpad, kpad,
+                          dropout_p=mha.dropout if mha.training else 0.0,
+                          bias_k=mha.bias_k, bias_v=mha.bias_v, add_zero_attn=mha.add_zero_attn)[0]
 
     def forward(self, q, k, v, attn_mask=None):
         if len(self.mixer) > 1:

@@ -145,6 +145,34 @@ def _loss_type_of(cfg):
     return cfg.loss_type
 
 
+def _attention_maps(model, inputs, average_heads):
+    """(model(*inputs), maps) from one eval, no-grad forward with every MultiheadAttention of the model
+    recording: maps is an OrderedDict from the attention's named_modules() path to its weights,
+    [B, Tq, Tk] (average_heads) or [B, heads, Tq, Tk], for the attentions the forward reached.  The
+    recording switches, what the modules held in last_weights and the train / eval mode are put back,
+    also when the forward raises.  The fused schedules decline a recording model, so this forward runs
+    module by module; the maps are rebuilt by mrg_attention_weights (cost not measured)."""
+    from .layers import MultiheadAttention
+    atts = [(n, m) for n, m in model.named_modules() if isinstance(m, MultiheadAttention)]
+    was = [(m.record_weights, m.last_weights) for _, m in atts]
+    modes = [(m, m.training) for m in model.modules()]
+    try:
+        for _, m in atts:
+            m.record_weights = "mean" if average_heads else "heads"
+            m.last_weights = None
+        model.eval()
+        with torch.no_grad():
+            y = model(*inputs)
+        maps = OrderedDict((n, m.last_weights) for n, m in atts if m.last_weights is not None)
+    finally:
+        for (_, m), (rec, last) in zip(atts, was):
+            m.record_weights = rec
+            m.last_weights = last
+        for m, mode in modes:
+            m.training = mode
+    return y, maps
+
+
 class _TorchLoss(nn.Module):
     """What ``lossfun()`` returns: a callable loss module backed by the fused kernel."""
 
@@ -266,6 +294,13 @@ class Metaformer(LightningSurface):
         y, _, hxs = self.metaformer(ms, [a, mp], hxs, (None, None, ms_mask),
                                     [(None, None, self_masks[0]), (None, None, self_masks[1])], [ma, mm])
         return y, hxs
+
+    def attention_maps(self, *inputs, average_heads=True):
+        """(y, maps) of one eval, no-grad forward(*inputs): y the prediction and maps an OrderedDict from
+        each attention's module path to its weights, [B, Tq, Tk] or, with average_heads=False,
+        [B, heads, Tq, Tk] (_attention_maps)."""
+        (y, _), maps = _attention_maps(self, inputs, average_heads)
+        return y, maps
 
     def lossfun(self):
         return _TorchLoss(self.model.loss_type, self.model.loss_reduction, self.huber_delta, self.smoothl1_beta)
@@ -666,6 +701,11 @@ class SimpleLSTM(LightningSurface):
             else None
         ae, me = out if out is not None else (enc_a.acostic_lstm(xa)[0], enc_m.motion_lstm(xm)[0])
         return self.motion_decoder(self.multimodal_att(me, ae))
+
+    def attention_maps(self, acoustic, motion, average_heads=True):
+        """(y, maps) of one eval, no-grad forward: one map [B, Tm, Ta] (or [B, heads, Tm, Ta]) per
+        cross-attention layer, keyed by its module path (_attention_maps)."""
+        return _attention_maps(self, (acoustic, motion), average_heads)
 
     def lossfun(self):
         return _TorchLoss("mse", "mean", 1.0, 1.0)
