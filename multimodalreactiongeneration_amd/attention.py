@@ -1,129 +1,40 @@
-"""The device dropout RNG, dropout, and multi-head attention."""
+"""Multi-head attention: the kernel calls (attn_fwd, attn_bwd) and nn.MultiheadAttention's forms on them."""
 import math
+from contextlib import nullcontext
+from types import SimpleNamespace
+from typing import NamedTuple, Optional
 
 import torch
 from torch.autograd import Function
 
 from . import _lib
 from .dense import _resln_bwd, _resln_fwd
+from .dropout import _drop_consts, _rng_draw
 from .gemm_ops import _dx_gemm, _fwd_gemm, _wgrad, _wt_note, gemm
-from .launch import _flush_touched, _gbuf, _keeps_precision, _probe, _ptr, _stream, _ws, zeros
-
-# --- dropout RNG (csrc/rng.h, rng.py): a per-device {seed, draw} state in device memory.  An op that
-# drops takes one draw with a one-thread kernel (a graph node: a replayed step takes fresh draws) and
-# keeps the 16-byte key tensor for its backward.  All DDP ranks share the default seed unless the
-# caller seeds per rank (manual_seed(base + rank)).
-_RNG = {}
+from .launch import _gbuf, _keeps_precision, _probe, _ptr, _stream, _ws, zeros
 
 
-def _i64(v: int) -> int:
-    v = int(v) & (2 ** 64 - 1)
-    return v - 2 ** 64 if v >= 2 ** 63 else v
+class MHASpec(NamedTuple):
+    """What an attention Function computes around the kernels (its first argument)."""
+    heads: int
+    causal: bool
+    eps: Optional[float] = None     # not None: return LN(attn + q) (ResidualConnection(MHAMixer))
+    p: float = 0.0                  # > 0: dropout on the attention probabilities, one draw
+    addq: bool = False              # return attn + q, the residual without a LayerNorm
+    zero_attn: bool = False         # add_zero_attn's always-visible zero key
+    weights: Optional[str] = None   # need_weights: None, "mean" (over the heads) or "heads"
 
 
-def _rng_device(device) -> torch.device:
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("the dropout RNG state lives on a HIP device")
-    return torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+def _save(ctx, **tensors):
+    """save_for_backward under names (None where the form has no such tensor); _saved gives them back."""
+    ctx.saved_names = tuple(tensors)
+    ctx.save_for_backward(*tensors.values())
 
 
-def _rng_state(device) -> torch.Tensor:
-    dev = _rng_device(device)
-    if dev.index not in _RNG:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("the dropout RNG state must exist before graph capture (run the step once, "
-                               "or call functional.manual_seed, first)")
-        from .rng import DEFAULT_SEED
-        _RNG[dev.index] = torch.tensor([_i64(DEFAULT_SEED), 0], dtype=torch.int64, device=dev)
-    return _RNG[dev.index]
+def _saved(ctx):
+    return SimpleNamespace(**dict(zip(ctx.saved_names, ctx.saved_tensors)))
 
 
-def manual_seed(seed: int, device=None) -> None:
-    """Reset the device's dropout RNG state to {seed, draw 0} (default seed: rng.DEFAULT_SEED)."""
-    set_rng_state(device, (seed, 0))
-
-
-def get_rng_state(device=None):
-    """(seed, draw) of the device's dropout RNG state as Python ints (synchronises)."""
-    seed, draw = _rng_state(device).tolist()
-    return seed & (2 ** 64 - 1), draw & (2 ** 64 - 1)
-
-
-def set_rng_state(device, state) -> None:
-    seed, draw = state
-    st = _rng_state(device)
-    st.copy_(torch.tensor([_i64(seed), _i64(draw)], dtype=torch.int64))
-
-
-def _drop_consts(p):
-    """(thr, scale_keep) of a dropout probability (ValueError outside [0, 1))."""
-    from .rng import threshold
-    return threshold(p), 1.0 / (1.0 - float(p))
-
-
-def _rng_draw(device) -> torch.Tensor:
-    """Take one draw: the op's key tensor {seed, draw} (int64 [2], device memory)."""
-    key = torch.empty(2, dtype=torch.int64, device=device)
-    _lib.check(_lib.load().mrg_rng_draw(_ptr(_rng_state(device)), _ptr(key), _stream()), "rng draw")
-    return key
-
-
-def dropout_keep_mask(key: torch.Tensor, n: int, p: float) -> torch.Tensor:
-    """uint8 [n]: the keep decisions functional.dropout makes with ``key`` (tests, debugging)."""
-    thr, _ = _drop_consts(p)
-    out = torch.empty(n, dtype=torch.uint8, device=key.device)
-    _lib.check(_lib.load().mrg_dropout_keep_mask(n, thr, _ptr(key), _ptr(out), _stream()), "dropout keep mask")
-    return out
-
-
-def attention_keep_mask(key: torch.Tensor, B: int, heads: int, Tq: int, Tk: int, p: float) -> torch.Tensor:
-    """uint8 [B, heads, Tq, Tk]: the keep decisions of an attention op that holds ``key``."""
-    thr, _ = _drop_consts(p)
-    out = torch.empty(B, heads, Tq, Tk, dtype=torch.uint8, device=key.device)
-    _lib.check(_lib.load().mrg_attention_keep_mask(B, heads, Tq, Tk, thr, _ptr(key), _ptr(out), _stream()),
-               "attention keep mask")
-    return out
-
-
-class _DropoutFn(Function):
-    """y = keep ? x / (1 - p) : 0 with one draw; the backward runs the same kernel on the gradient with
-    the saved key (no mask tensor is stored)."""
-
-    @staticmethod
-    def forward(ctx, x, p):
-        _lib.require_device(x)
-        thr, sk = _drop_consts(p)
-        xc = x.contiguous()
-        key = _rng_draw(xc.device)
-        y = torch.empty_like(xc)
-        _lib.check(_lib.load().mrg_dropout(xc.numel(), thr, sk, _ptr(key), _ptr(xc), _ptr(y), _stream()), "dropout")
-        ctx.save_for_backward(key)
-        ctx.consts = (thr, sk)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        _flush_touched()
-        (key,) = ctx.saved_tensors
-        thr, sk = ctx.consts
-        g = dy.contiguous()
-        dx = torch.empty_like(g)
-        _lib.check(_lib.load().mrg_dropout(g.numel(), thr, sk, _ptr(key), _ptr(g), _ptr(dx), _stream()), "dropout bwd")
-        return dx, None
-
-
-def dropout(x, p):
-    """Inverted dropout (training mode) on the library's counter-based RNG.  p = 0 returns x."""
-    thr, _ = _drop_consts(p)
-    if x.dtype != torch.float32:
-        raise ValueError("functional.dropout: float32 tensor required")
-    if float(p) == 0.0:
-        return x
-    return _DropoutFn.apply(x, float(p))
-
-
-# ------------------------------------------------------------------ multi-head attention
 def visible_pairs(Tq, Tk, causal):
     """(query, key) pairs the block-causal rule admits per (sample, head) (gen_attention_mask rules)."""
     if not causal:
@@ -135,13 +46,59 @@ def visible_pairs(Tq, Tk, causal):
     return sum(min(i // r + 1, Tk) for i in range(Tq))
 
 
-def _attn_args(heads, Q, KV, O, lse, qpad, kpad, causal, scale):
-    """The leading arguments every attention entry point takes: shapes, Q, K and V (the two halves of
-    KV), O, the row log-sum-exps, the padding flags and the mask rule."""
-    B, Tq, E = Q.shape
-    Tk = KV.shape[1]
-    return (B, heads, Tq, Tk, E // heads, _ptr(Q), Tq * E, E, _ptr(KV), Tk * 2 * E, 2 * E, _ptr(KV, E), Tk * 2 * E,
-            2 * E, _ptr(O), Tq * E, E, _ptr(lse), _ptr(qpad), _ptr(kpad), int(causal), scale)
+def _attn_args(heads, Q, KV, O, lse, qpad, kpad, causal, scale, v=None, chunk=()):
+    """The leading arguments every attention entry point takes: shapes (then a chunk form's q_off, Tq_full), Q,
+    K and V, O, the row log-sum-exps, the padding flags and the mask rule.  KV is [B, Tk, 2E], keys then values
+    in a row; Q and O: B * Tq contiguous rows of E under any leading shape; v: the values are its first E columns."""
+    B, Tk, E2 = KV.shape
+    E = E2 // 2
+    Tq = Q.numel() // max(1, B * E)
+    return (B, heads, Tq, Tk, E // heads, *chunk, _ptr(Q), Tq * E, E, _ptr(KV), Tk * E2, E2,
+            _ptr(KV, E) if v is None else _ptr(v), Tk * E2, E2, _ptr(O), Tq * E, E, _ptr(lse), _ptr(qpad), _ptr(kpad),
+            int(causal), scale)
+
+
+def _bracket(name, probe, flops_per_pair, args, causal):
+    """The probe bracket of a launch with these leading arguments (nothing when not probe)."""
+    B, heads, Tq, Tk, D = args[:5]
+    return _probe(name, flops_per_pair * D * B * heads * visible_pairs(Tq, Tk, causal)) if probe else nullcontext()
+
+
+def attn_fwd(heads, Q, KV, O, lse, qpad, kpad, causal, scale, *, drop=None, v=None, probe=False,
+             what="attention fwd"):
+    """One forward launch of the attention kernels into O and lse; every forward call of the package.
+    drop = (thr, scale_keep, key): the dropout form (never bracketed); v: see _attn_args (V = K: v=KV);
+    probe: bracket the launch as "attn_fwd" for the per-kernel measurements."""
+    args = _attn_args(heads, Q, KV, O, lse, qpad, kpad, causal, scale, v)
+    lib = _lib.load()
+    if drop is not None:
+        rc = lib.mrg_attention_fwd_dropout(*args, *drop[:2], _ptr(drop[2]), _stream())
+    else:
+        with _bracket("attn_fwd", probe, 4.0, args, causal):
+            rc = lib.mrg_attention_fwd(*args, _stream())
+    _lib.check(rc, what)
+
+
+def attn_bwd(heads, Q, KV, O, lse, qpad, kpad, causal, scale, dO, dQ, dKV, ws, *, drop=None, chunk=None, passes=3,
+             kv_accumulate=0, probe=False, what="attention bwd"):
+    """One backward call of the attention kernels into dQ and the two halves of dKV; every backward call of the
+    package.  dO: rows like Q's, or one row [E] taken for every query (strides 0); ws: the delta workspace
+    (mrg_attention_bwd_workspace_bytes); drop, probe ("attn_bwd") as in attn_fwd; chunk = (q_off, Tq_full): the chunk
+    form with its passes and kv_accumulate (include/mrg.h: lse, ws, qpad the whole sequence's; no dropout variant)."""
+    args = _attn_args(heads, Q, KV, O, lse, qpad, kpad, causal, scale, chunk=chunk or ())
+    Tq, Tk = args[2:4]
+    E = KV.shape[2] // 2
+    lib = _lib.load()
+    args += (_ptr(dO), *((0, 0) if dO.dim() == 1 else (Tq * E, E)), _ptr(dQ), Tq * E, E, _ptr(dKV), Tk * 2 * E, 2 * E,
+             _ptr(dKV, E), Tk * 2 * E, 2 * E)
+    if chunk is not None:
+        rc = lib.mrg_attention_bwd_chunk(*args, passes, kv_accumulate, _ptr(ws), _stream())
+    elif drop is not None:
+        rc = lib.mrg_attention_bwd_dropout(*args, _ptr(ws), *drop[:2], _ptr(drop[2]), _stream())
+    else:
+        with _bracket("attn_bwd", probe, 10.0, args, causal):
+            rc = lib.mrg_attention_bwd(*args, _ptr(ws), _stream())
+    _lib.check(rc, what)
 
 
 class _MHAFn(Function):
@@ -149,24 +106,13 @@ class _MHAFn(Function):
     @_keeps_precision
     def forward(ctx, spec, q_in, kv_in, in_w, in_b, out_w, out_b, qpad, kpad, gamma=None, beta=None,
                 bias_k=None, bias_v=None):
-        # eps not None: return LN(attn + q) (ResidualConnection(MHAMixer)); p > 0: dropout on the
-        # attention probabilities with one draw, the key saved for the backward
-        # addq: return attn + q (the residual without a LayerNorm), q added by the output projection's
-        # epilogue 3
-        heads, causal, eps, *rest = spec
-        p = rest[0] if rest else 0.0
-        addq = bool(rest[1]) if len(rest) > 1 else False
-        # extra always-visible keys (add_bias_kv: bias_k / bias_v; add_zero_attn: rest[2]): one merge launch
-        # after the attention kernel (_extra_fwd)
-        zero_attn = bool(rest[2]) if len(rest) > 2 else False
-        # need_weights (rest[3]: None, "mean" or "heads"): a second, non-differentiable output, the attention
-        # probabilities rebuilt from Q, K and lse by one more launch (_weights)
-        want = rest[3] if len(rest) > 3 else None
+        # p > 0: one draw, its key saved for the backward; addq: by the output projection's epilogue 3; extra
+        # keys (bias_k / bias_v, zero_attn): one merge launch (_extra_fwd); weights: one more launch (_weights)
+        heads, causal, eps, p, addq, zero_attn, want = spec
         _lib.require_device(q_in)
         dev = q_in.device
         B, Tq, E = q_in.shape
         Tk = kv_in.shape[1]
-        D = E // heads
         q2 = q_in.contiguous()
         kv2 = kv_in.contiguous()
         Q = torch.empty(B, Tq, E, device=dev, dtype=torch.float32)
@@ -175,18 +121,9 @@ class _MHAFn(Function):
         _fwd_gemm(B * Tk, 2 * E, E, _ptr(kv2), E, in_w[E:], _ptr(KV), 2 * E, bias=_ptr(in_b, E), device=dev)
         O = torch.empty(B, Tq, E, device=dev, dtype=torch.float32)
         lse = torch.empty(B, heads, Tq, device=dev, dtype=torch.float32)
-        scale = 1.0 / math.sqrt(D)
-        lib = _lib.load()
-        args = _attn_args(heads, Q, KV, O, lse, qpad, kpad, causal, scale)
-        drop = None
-        if p > 0.0:
-            thr, sk = _drop_consts(p)
-            drop = (thr, sk, _rng_draw(dev))
-            rc = lib.mrg_attention_fwd_dropout(*args, thr, sk, _ptr(drop[2]), _stream())
-        else:
-            with _probe("attn_fwd", 4.0 * D * B * heads * visible_pairs(Tq, Tk, causal)):
-                rc = lib.mrg_attention_fwd(*args, _stream())
-        _lib.check(rc, "attention fwd")
+        scale = 1.0 / math.sqrt(E // heads)
+        drop = (*_drop_consts(p), _rng_draw(dev)) if p > 0.0 else None
+        attn_fwd(heads, Q, KV, O, lse, qpad, kpad, causal, scale, drop=drop, probe=True)
         if bias_k is not None or zero_attn:
             _extra_fwd(heads, Q, bias_k, bias_v, zero_attn, scale, O, lse, Tk, drop)
         out = torch.empty(B, Tq, E, device=dev, dtype=torch.float32)
@@ -197,16 +134,14 @@ class _MHAFn(Function):
         _wt_note(out_w, B * Tq)
         _wt_note(in_w[:E], B * Tq, ctx.needs_input_grad[1])
         _wt_note(in_w[E:], B * Tk, ctx.needs_input_grad[2])
-        extra = []
+        ln = {}
         res = out
         if eps is not None:
             u, mean, rstd = _resln_fwd(out.view(B * Tq, E), q2.view(B * Tq, E), gamma, beta, eps)
             res = u.view(B, Tq, E)
-            extra = [out, gamma, beta, mean, rstd]
-        if bias_k is not None:
-            extra = extra + [bias_k, bias_v]
-        ctx.save_for_backward(q2, kv2, Q, KV, O, lse, in_w, in_b, out_w, out_b, qpad, kpad, *extra)
-        ctx.has_bias_kv = bias_k is not None
+            ln = dict(out=out, gamma=gamma, beta=beta, mean=mean, rstd=rstd)
+        _save(ctx, q2=q2, kv2=kv2, Q=Q, KV=KV, O=O, lse=lse, in_w=in_w, in_b=in_b, out_w=out_w, out_b=out_b,
+              qpad=qpad, kpad=kpad, **ln, bias_k=bias_k, bias_v=bias_v)
         ctx.spec = (heads, causal, scale, eps is not None)
         ctx.addq = addq
         ctx.drop = drop
@@ -219,19 +154,17 @@ class _MHAFn(Function):
     @staticmethod
     @_keeps_precision
     def backward(ctx, dout, _dweights=None):
-        saved = ctx.saved_tensors
-        q2, kv2, Q, KV, O, lse, in_w, in_b, out_w, out_b, qpad, kpad = saved[:12]
+        s = _saved(ctx)
+        q2, kv2, Q, KV, O, lse, in_w, in_b, out_w, out_b, qpad, kpad = (
+            s.q2, s.kv2, s.Q, s.KV, s.O, s.lse, s.in_w, s.in_b, s.out_w, s.out_b, s.qpad, s.kpad)
         heads, causal, scale, resln = ctx.spec
         B, Tq, E = q2.shape
         Tk = kv2.shape[1]
-        D = E // heads
         dev = dout.device
-        lib = _lib.load()
         g = None  # residual-branch gradient of LN(attn + q), added by the dq GEMM's epilogue
         if resln:
-            out, gamma, beta, mean, rstd = saved[12:17]
-            g = _resln_bwd(dout.reshape(B * Tq, E).contiguous(), out.view(B * Tq, E), q2.view(B * Tq, E),
-                           gamma, beta, mean, rstd)
+            g = _resln_bwd(dout.reshape(B * Tq, E).contiguous(), s.out.view(B * Tq, E), q2.view(B * Tq, E),
+                           s.gamma, s.beta, s.mean, s.rstd)
             do2 = g.view(B, Tq, E)
         else:
             do2 = dout.contiguous()
@@ -242,19 +175,10 @@ class _MHAFn(Function):
         _wgrad(_ptr(do2), E, _ptr(O), E, B * Tq, E, E, _gbuf(out_w), dev, gb=_gbuf(out_b), keep=(do2, O))
         dQ = torch.empty(B, Tq, E, device=dev, dtype=torch.float32)
         dKV = torch.empty(B, Tk, 2 * E, device=dev, dtype=torch.float32)
-        ws = _ws(lib.mrg_attention_bwd_workspace_bytes(B, heads, Tq), dev)
-        args = _attn_args(heads, Q, KV, O, lse, qpad, kpad, causal, scale) + (
-            _ptr(dO), Tq * E, E, _ptr(dQ), Tq * E, E, _ptr(dKV), Tk * 2 * E, 2 * E, _ptr(dKV, E), Tk * 2 * E, 2 * E,
-            _ptr(ws))
-        if ctx.drop is not None:
-            thr, sk, key = ctx.drop
-            rc = lib.mrg_attention_bwd_dropout(*args, thr, sk, _ptr(key), _stream())
-        else:
-            with _probe("attn_bwd", 10.0 * D * B * heads * visible_pairs(Tq, Tk, causal)):
-                rc = lib.mrg_attention_bwd(*args, _stream())
-        _lib.check(rc, "attention bwd")
-        if ctx.has_bias_kv:   # the zero key alone has no gradient: the merged O / lse did it all
-            _extra_bwd(heads, Q, KV, O, lse, qpad, kpad, causal, scale, saved[-2:], dO, dQ, dKV, ctx.drop)
+        ws = _ws(_lib.load().mrg_attention_bwd_workspace_bytes(B, heads, Tq), dev)
+        attn_bwd(heads, Q, KV, O, lse, qpad, kpad, causal, scale, dO, dQ, dKV, ws, drop=ctx.drop, probe=True)
+        if s.bias_k is not None:   # the zero key alone has no gradient: the merged O / lse did it all
+            _extra_bwd(heads, Q, KV, O, lse, qpad, kpad, causal, scale, (s.bias_k, s.bias_v), dO, dQ, dKV, ctx.drop)
         gw, gb = _gbuf(in_w), _gbuf(in_b)
         _wgrad(_ptr(dQ), E, _ptr(q2), E, B * Tq, E, E, None if gw is None else gw[:E], dev,
                gb=None if gb is None else gb[:E], keep=(dQ, q2))
@@ -333,21 +257,15 @@ def _extra_bwd(heads, Q, KV, O, lse, qpad, kpad, causal, scale, bias_kv, dO, dQ,
         pk = torch.empty(B, Tq, E, device=dev, dtype=torch.float32)
         lse_main = torch.empty(B, heads, Tq, device=dev, dtype=torch.float32)
         cbuf = torch.empty(B, heads, Tq, device=dev, dtype=torch.float32)
-        _lib.check(lib.mrg_attention_fwd(B, heads, Tq, Tk, D, _ptr(Q), Tq * E, E, _ptr(KV), Tk * 2 * E, 2 * E,
-                                         _ptr(KV), Tk * 2 * E, 2 * E, _ptr(pk), Tq * E, E, _ptr(lse_main),
-                                         _ptr(qpad), _ptr(kpad), int(causal), scale, _stream()),
-                   "attention extra keys: P K")
+        attn_fwd(heads, Q, KV, pk, lse_main, qpad, kpad, causal, scale, v=KV, what="attention extra keys: P K")
     _lib.check(lib.mrg_attention_extra_bwd(
         B, heads, Tq, D, _ptr(Q), Tq * E, E, _ptr(bias_k), _ptr(bias_v), scale, _ptr(O), Tq * E, E, _ptr(lse),
         _ptr(dO), Tq * E, E, _ptr(dQ), Tq * E, E, _ptr(gk), _ptr(gv), acc, Tk, thr, sk, _ptr(key),
         _ptr(pk), Tq * E, E, _ptr(lse_main), _ptr(cbuf), _ptr(ws), _stream()), "attention extra keys bwd")
     if cbuf is not None:
         z = zeros(E, device=dev)   # dO = 0 for every query: one row, strides 0
-        _lib.check(lib.mrg_attention_bwd_chunk(
-            B, heads, Tq, Tk, D, 0, Tq, _ptr(Q), Tq * E, E, _ptr(KV), Tk * 2 * E, 2 * E, _ptr(KV, E), Tk * 2 * E,
-            2 * E, _ptr(O), Tq * E, E, _ptr(lse), _ptr(qpad), _ptr(kpad), int(causal), scale, _ptr(z), 0, 0,
-            _ptr(dQ), Tq * E, E, _ptr(dKV), Tk * 2 * E, 2 * E, _ptr(dKV, E), Tk * 2 * E, 2 * E, 2, 1, _ptr(cbuf),
-            _stream()), "attention extra keys: dK delta term")
+        attn_bwd(heads, Q, KV, O, lse, qpad, kpad, causal, scale, z, dQ, dKV, cbuf, chunk=(0, Tq), passes=2,
+                 kv_accumulate=1, what="attention extra keys: dK delta term")
 
 
 class _MHAOneKeyFn(Function):
@@ -361,9 +279,8 @@ class _MHAOneKeyFn(Function):
 
     @staticmethod
     @_keeps_precision
-    def forward(ctx, eps, q_in, kv_in, in_w, in_b, out_w, out_b, qpad, kpad, gamma=None, beta=None):
-        addq = eps == "add"   # attn + q without a LayerNorm: q added by the output projection's epilogue 3
-        eps = None if addq else eps
+    def forward(ctx, spec, q_in, kv_in, in_w, in_b, out_w, out_b, qpad, kpad, gamma=None, beta=None):
+        eps, addq = spec.eps, spec.addq   # addq: q added by the output projection's epilogue 3
         _lib.require_device(q_in)
         dev = q_in.device
         B, _, E = q_in.shape
@@ -380,12 +297,12 @@ class _MHAOneKeyFn(Function):
         kw = dict(epi=3, aux=_ptr(q2), ldaux=E) if addq else {}
         gemm(B, E, E, _ptr(O), 0, E, _ptr(out_w), 1, E, _ptr(out), E, bias=_ptr(out_b), device=dev, **kw)
         res = out
-        extra = []
+        ln = {}
         if eps is not None:
             u, mean, rstd = _resln_fwd(out, q2, gamma, beta, eps)
             res = u
-            extra = [out, gamma, beta, mean, rstd]
-        ctx.save_for_backward(q2, kv2, O, in_w, in_b, out_w, out_b, *extra)
+            ln = dict(out=out, gamma=gamma, beta=beta, mean=mean, rstd=rstd)
+        _save(ctx, q2=q2, kv2=kv2, O=O, in_w=in_w, in_b=in_b, out_w=out_w, out_b=out_b, **ln)
         ctx.hide = hide
         ctx.resln = eps is not None
         ctx.addq = addq
@@ -394,14 +311,13 @@ class _MHAOneKeyFn(Function):
     @staticmethod
     @_keeps_precision
     def backward(ctx, dout):
-        saved = ctx.saved_tensors
-        q2, kv2, O, in_w, in_b, out_w, out_b = saved[:7]
+        s = _saved(ctx)
+        q2, kv2, O, in_w, in_b, out_w, out_b = s.q2, s.kv2, s.O, s.in_w, s.in_b, s.out_w, s.out_b
         B, E = q2.shape
         dev = dout.device
         g = None
         if ctx.resln:
-            out, gamma, beta, mean, rstd = saved[7:]
-            g = _resln_bwd(dout.reshape(B, E).contiguous(), out, q2, gamma, beta, mean, rstd)
+            g = _resln_bwd(dout.reshape(B, E).contiguous(), s.out, q2, s.gamma, s.beta, s.mean, s.rstd)
             do2 = g
         else:
             do2 = dout.reshape(B, E).contiguous()
@@ -428,11 +344,12 @@ def _one_key(q, kv):
 
 
 def _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
-         eps=None, ln=(), addq=False, bias_k=None, bias_v=None, add_zero_attn=False, need_weights=False,
+         eps, ln, addq, *, bias_k=None, bias_v=None, add_zero_attn=False, need_weights=False,
          average_attn_weights=True):
     """The attention Function for these shapes; eps not None: LN(. + q) with ln = (gamma, beta); addq:
-    . + q without a LayerNorm.  bias_k / bias_v ([1, 1, E] or [E]; both or neither) and add_zero_attn:
-    nn.MultiheadAttention's extra keys, visible to every query whatever the mask rules say.  With one the
+    . + q without a LayerNorm.  The keywords (the three public forms pass theirs on): bias_k / bias_v
+    ([1, 1, E] or [E]; both or neither) and add_zero_attn: nn.MultiheadAttention's extra keys, visible to
+    every query whatever the mask rules say.  With one the
     call is always the unchunked _MHAFn: the one-key form does not apply (there is more than one key),
     and the query-chunked schedules (encoder_stack, integrate) never see such a module
     (forms.integrator_form declines it), so the merge has no chunk form.
@@ -447,53 +364,44 @@ def _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causa
     want = ("mean" if average_attn_weights else "heads") if need_weights else None
     if (bias_k is None) != (bias_v is None):
         raise ValueError("mha: bias_k and bias_v come together")
-    if bias_k is not None or add_zero_attn:
-        E = q.shape[-1]
-        for t in (bias_k, bias_v):
-            if t is not None and (t.numel() != E or t.dtype != torch.float32 or not t.is_contiguous()
-                                  or t.device != q.device):
-                raise ValueError("mha: bias_k / bias_v must be contiguous float32 [1, 1, E] on the query's device")
-        lnp = ln if ln else (None, None)
-        spec = (heads, bool(causal), eps, p, bool(addq), bool(add_zero_attn)) + ((want,) if want else ())
-        return _MHAFn.apply(spec, q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, qpad, kpad, *lnp,
-                            bias_k, bias_v)
-    if p == 0.0 and _one_key(q, kv):   # with dropout the single probability 1 is still dropped: _MHAFn
-        out = _MHAOneKeyFn.apply("add" if addq else eps, q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias,
-                                 qpad, kpad, *ln)
+    for t in (bias_k, bias_v):
+        if t is not None and (t.numel() != q.shape[-1] or t.dtype != torch.float32 or not t.is_contiguous()
+                              or t.device != q.device):
+            raise ValueError("mha: bias_k / bias_v must be contiguous float32 [1, 1, E] on the query's device")
+    extra = bias_k is not None or add_zero_attn
+    spec = MHASpec(heads, bool(causal), eps, p, bool(addq), bool(add_zero_attn), want)
+    args = (spec, q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, qpad, kpad, *ln)
+    if not extra and p == 0.0 and _one_key(q, kv):   # with dropout the single probability 1 is still dropped: _MHAFn
+        out = _MHAOneKeyFn.apply(*args)
         return (out, _one_key_weights(q, heads, qpad, kpad, want == "mean")) if want else out
-    spec = (heads, bool(causal), eps, p, bool(addq)) + ((False, want) if want else ())
-    return _MHAFn.apply(spec, q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, qpad, kpad, *ln)
+    return _MHAFn.apply(*args, bias_k, bias_v)
 
 
 def mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal=False,
-        qpad=None, kpad=None, dropout_p=0.0, bias_k=None, bias_v=None, add_zero_attn=False,
-        need_weights=False, average_attn_weights=True):
+        qpad=None, kpad=None, dropout_p=0.0, **kw):
     """nn.MultiheadAttention(batch_first, kdim=vdim=E)(q, kv, kv) with the reference mask rules.
     dropout_p > 0: dropout on the attention probabilities (the module's training mode).
-    bias_k / bias_v, add_zero_attn: the module's add_bias_kv / add_zero_attn keys (see _mha).
-    need_weights: (out, weights) with the attention probabilities, no gradient through them (see _mha)."""
+    Keywords (_mha's): bias_k / bias_v, add_zero_attn: the module's add_bias_kv / add_zero_attn keys;
+    need_weights, average_attn_weights: (out, weights), the attention probabilities without a gradient."""
     return _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
-                bias_k=bias_k, bias_v=bias_v, add_zero_attn=add_zero_attn, need_weights=need_weights,
-                average_attn_weights=average_attn_weights)
+                None, (None, None), False, **kw)
 
 
 def mha_residual_layernorm(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, gamma, beta,
-                           eps=1e-5, causal=False, qpad=None, kpad=None, dropout_p=0.0, bias_k=None, bias_v=None,
-                           add_zero_attn=False, need_weights=False, average_attn_weights=True):
+                           eps=1e-5, causal=False, qpad=None, kpad=None, dropout_p=0.0, **kw):
     """LN(MHA(q, kv, kv) + q): ResidualConnection(MHAMixer) (mixer_block.py:567-603); the query
-    projection's input-gradient GEMM takes the residual gradient in its epilogue."""
+    projection's input-gradient GEMM takes the residual gradient in its epilogue.  Keywords as mha's."""
     return _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
-                float(eps), (gamma, beta), bias_k=bias_k, bias_v=bias_v, add_zero_attn=add_zero_attn,
-                need_weights=need_weights, average_attn_weights=average_attn_weights)
+                float(eps), (gamma, beta), False, **kw)
 
 
 def mha_residual(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal=False,
-                 qpad=None, kpad=None, dropout_p=0.0, bias_k=None, bias_v=None, add_zero_attn=False,
-                 need_weights=False, average_attn_weights=True):
+                 qpad=None, kpad=None, dropout_p=0.0, **kw):
     """MHA(q, kv, kv) + q: ResidualConnection(MHAMixer) without a LayerNorm.  q is added by the output
     projection's GEMM (epilogue 3) in both forms of mha, and the gradient of the sum by the query
     projection's input-gradient GEMM (the one-key form has no query projection: there dq is the
-    gradient itself)."""
+    gradient itself).  Keywords as mha's."""
     return _mha(q, kv, in_proj_weight, in_proj_bias, out_weight, out_bias, heads, causal, qpad, kpad, dropout_p,
-                addq=True, bias_k=bias_k, bias_v=bias_v, add_zero_attn=add_zero_attn, need_weights=need_weights,
-                average_attn_weights=average_attn_weights)
+                None, (None, None), True, **kw)
+
+

@@ -800,20 +800,6 @@ __global__ __launch_bounds__(512) void attn_bwd_fused_kernel(AttnArgs a) {
 
 using namespace mrg;
 
-static AttnArgs attn_base(int B, int Hh, int Tq, int Tk, const float* q, long q_bs, long q_ts,
-                          const float* k, long k_bs, long k_ts, const float* v, long v_bs, long v_ts,
-                          const float* o, long o_bs, long o_ts, const float* lse,
-                          const unsigned char* qpad, const unsigned char* kpad, int causal, float scale) {
-  AttnArgs a;
-  memset(&a, 0, sizeof(a));
-  a.q = q; a.q_bs = q_bs; a.q_ts = q_ts; a.k = k; a.k_bs = k_bs; a.k_ts = k_ts;
-  a.v = v; a.v_bs = v_bs; a.v_ts = v_ts; a.o = const_cast<float*>(o); a.o_bs = o_bs; a.o_ts = o_ts;
-  a.lse = const_cast<float*>(lse); a.qpad = qpad; a.kpad = kpad; a.B = B; a.Hh = Hh; a.Tq = Tq; a.Tk = Tk;
-  a.causal = causal; a.scale = scale;
-  a.q_off = 0; a.Tqf = Tq; a.qp_bs = Tq; a.kv_acc = 0; a.st_ld = Tq; a.st_off = 0;
-  return a;
-}
-
 // single-pass backward (attn_bwd_fused_kernel) where it applies: 1 (default) or 0 (MRG_ATTN_FUSED,
 // mrg_attention_set_fused: the two-pass form always)
 static int g_attn_fused = env_int("MRG_ATTN_FUSED", 1);
@@ -824,8 +810,50 @@ MRG_API int mrg_attention_set_fused(int on) {
   return prev;
 }
 
-static bool rows16(const float* p, long bs, long ts) {
-  return p == nullptr || ((((uintptr_t)p) & 15) == 0 && (bs & 3) == 0 && (ts & 3) == 0);
+// What an entry point has beside the common arguments (a form without one hands in nullptr).
+struct AttnGrads {   // the backward forms
+  const float* dout; long do_bs, do_ts; float* dq; long dq_bs, dq_ts; float* dk; long dk_bs, dk_ts;
+  float* dv; long dv_bs, dv_ts; float* workspace;
+};
+struct AttnChunk { int q_off, Tq_full, passes, kv_accumulate; };   // the chunk forms (passes, kv_accumulate: backward)
+struct AttnDrop { unsigned int thr; float scale_keep; const unsigned long long* key; };   // the dropout forms
+
+// One call as the two launch paths (attn_forward, attn_backward) see it.  passes (backward): 1 = dQ (+ delta),
+// 2 = dK / dV, 3 = both; drop and chunk are never both set (the chunk forms have no dropout variant).
+struct AttnCall {
+  AttnArgs a;
+  int D, passes;
+  bool drop, chunk;
+  hipStream_t stream;
+};
+
+// The only place that fills the kernels' argument block (qvec / ovec / dkvvec excepted: the launch
+// paths set them where they check the alignment).  Checks nothing and launches nothing.
+static AttnCall attn_call(int B, int Hh, int Tq, int Tk, int D, const float* q, long q_bs, long q_ts,
+                          const float* k, long k_bs, long k_ts, const float* v, long v_bs, long v_ts,
+                          const float* o, long o_bs, long o_ts, const float* lse, const unsigned char* qpad,
+                          const unsigned char* kpad, int causal, float scale, hipStream_t stream,
+                          const AttnGrads* g, const AttnChunk* ch, const AttnDrop* dr) {
+  AttnCall c;
+  memset(&c, 0, sizeof(c));
+  c.D = D; c.drop = dr != nullptr; c.chunk = ch != nullptr; c.passes = ch ? ch->passes : 3; c.stream = stream;
+  AttnArgs& a = c.a;
+  a.q = q; a.q_bs = q_bs; a.q_ts = q_ts; a.k = k; a.k_bs = k_bs; a.k_ts = k_ts;
+  a.v = v; a.v_bs = v_bs; a.v_ts = v_ts; a.o = const_cast<float*>(o); a.o_bs = o_bs; a.o_ts = o_ts;
+  a.lse = const_cast<float*>(lse); a.kpad = kpad; a.B = B; a.Hh = Hh; a.Tq = Tq; a.Tk = Tk;
+  a.causal = causal; a.scale = scale;
+  // the Tq rows are rows [q_off, q_off + Tq) of Tqf (a plain call: all of them); lse, delta and qpad are the whole
+  // sequence's, this call's columns at q_off
+  const int q_off = ch ? ch->q_off : 0, Tqf = ch ? ch->Tq_full : Tq;
+  a.qpad = qpad ? qpad + q_off : nullptr; a.q_off = q_off; a.Tqf = Tqf; a.qp_bs = Tqf; a.st_ld = Tqf; a.st_off = q_off;
+  a.kv_acc = (ch && ch->kv_accumulate) ? 1 : 0;
+  if (g) {
+    a.dout = g->dout; a.do_bs = g->do_bs; a.do_ts = g->do_ts; a.dlt = g->workspace;
+    a.dq = g->dq; a.dq_bs = g->dq_bs; a.dq_ts = g->dq_ts; a.dk = g->dk; a.dk_bs = g->dk_bs; a.dk_ts = g->dk_ts;
+    a.dv = g->dv; a.dv_bs = g->dv_bs; a.dv_ts = g->dv_ts;
+  }
+  if (dr) { a.rkey = dr->key; a.thr = dr->thr; a.keep_scale = dr->scale_keep; }
+  return c;
 }
 
 static int attn_check(int D, int Tq, int Tk, int causal) {
@@ -835,30 +863,93 @@ static int attn_check(int D, int Tq, int Tk, int causal) {
   return 0;
 }
 
-#define MRG_ATTN_DISPATCH(KERNEL, grid, args)                          \
-  switch (D) {                                                         \
-    case 8: klaunch(KERNEL<8>, grid, 256, 0, stream, args); break;         \
-    case 16: klaunch(KERNEL<16>, grid, 256, 0, stream, args); break;       \
-    case 32: klaunch(KERNEL<32>, grid, 256, 0, stream, args); break;       \
-    case 64: klaunch(KERNEL<64>, grid, 256, 0, stream, args); break;       \
-  }
+static int drop_check(unsigned int thr, float scale_keep, const unsigned long long* key, int B, int Hh) {
+  MRG_REQUIRE(key != nullptr && (((uintptr_t)key) & 7) == 0, "attention dropout: key (2 x uint64, 8-B aligned) required");
+  MRG_REQUIRE(scale_keep >= 1.0f && std::isfinite(scale_keep), "attention dropout: scale_keep = 1 / (1 - p), p in [0, 1)");
+  MRG_REQUIRE((long)B * Hh < 0xFFFFFFFFL, "attention dropout: B * heads too large");
+  (void)thr;
+  return 0;
+}
 
+static int chunk_check(const char* pass, int q_off, int Tq, int Tq_full) {
+  MRG_REQUIRE(q_off >= 0 && Tq >= 0 && q_off + Tq <= Tq_full, "attention %s chunk: rows [%d, %d) outside %d", pass,
+              q_off, q_off + Tq, Tq_full);
+  return 0;
+}
+
+// KERNEL<D, DROP> of the call c on grid: the one dispatch over the head width and the dropout flag
+#define MRG_ATTN_CASE(KERNEL, DD, grid, c)                                        \
+  case DD: (c).drop ? klaunch(KERNEL<DD, true>, grid, 256, 0, (c).stream, (c).a)  \
+                    : klaunch(KERNEL<DD, false>, grid, 256, 0, (c).stream, (c).a); break;
+#define MRG_ATTN_DISPATCH(KERNEL, grid, c)                                                                  \
+  switch ((c).D) { MRG_ATTN_CASE(KERNEL, 8, grid, c) MRG_ATTN_CASE(KERNEL, 16, grid, c)                    \
+                   MRG_ATTN_CASE(KERNEL, 32, grid, c) MRG_ATTN_CASE(KERNEL, 64, grid, c) }
+
+static int attn_forward(AttnCall c) {
+  AttnArgs& a = c.a;
+  if (a.B == 0 || a.Tq == 0) return 0;
+  MRG_REQUIRE(rows16(a.k, a.k_bs, a.k_ts) && rows16(a.v, a.v_bs, a.v_ts),
+              "attention fwd: K/V rows must be 16-B aligned (strides multiple of 4 floats)");
+  a.qvec = rows16(a.q, a.q_bs, a.q_ts) && (c.D % 4) == 0;
+  a.ovec = rows16(a.o, a.o_bs, a.o_ts) && (c.D % 4) == 0;
+  dim3 grid(a.Hh, a.B, (a.Tq + 63) / 64);
+  MRG_ATTN_DISPATCH(attn_fwd_kernel, grid, c);
+  return check_launch(c.drop ? "attn_fwd_kernel<dropout>" : "attn_fwd_kernel");
+}
+
+static int attn_backward(AttnCall c) {
+  AttnArgs& a = c.a;
+  if (a.B == 0 || a.Tq == 0 || a.Tk == 0) return 0;
+  MRG_REQUIRE(rows16(a.q, a.q_bs, a.q_ts) && rows16(a.k, a.k_bs, a.k_ts) && rows16(a.v, a.v_bs, a.v_ts) &&
+              rows16(a.dout, a.do_bs, a.do_ts), "attention bwd: Q/K/V/dO rows must be 16-B aligned");
+  MRG_REQUIRE(a.dlt != nullptr, "attention bwd: workspace (B*heads*%s floats) required", c.chunk ? "Tq_full" : "Tq");
+  MRG_REQUIRE(c.passes >= 1 && c.passes <= 3, "attention bwd chunk: passes %d (1 dQ, 2 dK/dV, 3 both)", c.passes);
+  a.qvec = 1;  // required above
+  a.ovec = rows16(a.o, a.o_bs, a.o_ts);
+  a.dkvvec = rows16(a.dk, a.dk_bs, a.dk_ts) && rows16(a.dv, a.dv_bs, a.dv_ts);
+  if (!c.drop && !c.chunk && g_attn_fused && c.D == 64 && a.Tq <= FTQ && a.ovec && a.dkvvec &&
+      rows16(a.dq, a.dq_bs, a.dq_ts)) {
+    static bool attr[64] = {};   // single-pass kernel (plain backward only): its LDS size attribute, once per device
+    constexpr int bytes = FusedLds<64>::FLOATS * (int)sizeof(float);
+    static_assert(bytes <= 160 * 1024, "fused attention backward: LDS layout exceeds a CU's 160 KB");
+    int dev = 0;
+    MRG_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !attr[dev]) {
+      MRG_HIP(hipFuncSetAttribute((const void*)attn_bwd_fused_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  bytes));
+      if (dev >= 0 && dev < 64) attr[dev] = true;
+    }
+    klaunch(attn_bwd_fused_kernel<64>, dim3(a.Hh, a.B), 512, bytes, c.stream, a);
+    return check_launch("attn_bwd_fused_kernel");
+  }
+  if (c.passes & 1) {   // dQ, and delta = rowsum(dO * O) into the workspace (the dK / dV pass reads it there)
+    dim3 gq(a.Hh, a.B, (a.Tq + 63) / 64);
+    MRG_ATTN_DISPATCH(attn_bwd_dq_kernel, gq, c);
+    if (check_launch(c.drop ? "attn_bwd_dq_kernel<dropout>" : "attn_bwd_dq_kernel")) return 1;
+  }
+  if (!(c.passes & 2)) return 0;
+  // accumulating: only the key blocks the chunk's last query can see (the rest get nothing)
+  int tk = a.Tk;
+  if (a.kv_acc && a.causal) {
+    const int gl = a.q_off + a.Tq - 1;
+    tk = (a.Tk >= a.Tqf) ? (gl + 1) * (a.Tk / a.Tqf) : gl / (a.Tqf / a.Tk) + 1;
+    tk = tk < a.Tk ? tk : a.Tk;
+  }
+  dim3 gk(a.Hh, a.B, (tk + 63) / 64);
+  MRG_ATTN_DISPATCH(attn_bwd_dkv_kernel, gk, c);
+  return check_launch(c.drop ? "attn_bwd_dkv_kernel<dropout>" : "attn_bwd_dkv_kernel");
+}
+
+// The entry points: each form's own argument checks (attn_check against the whole sequence's queries), then
+// the shared path.  The dropout forms: nn.MultiheadAttention(dropout = p) in training.
 MRG_API int mrg_attention_fwd(int B, int Hh, int Tq, int Tk, int D,
                               const float* q, long q_bs, long q_ts, const float* k, long k_bs, long k_ts,
                               const float* v, long v_bs, long v_ts, float* o, long o_bs, long o_ts,
                               float* lse, const unsigned char* qpad, const unsigned char* kpad,
                               int causal, float scale, hipStream_t stream) {
   if (int e = attn_check(D, Tq, Tk, causal)) return e;
-  if (B == 0 || Tq == 0) return 0;
-  MRG_REQUIRE(rows16(k, k_bs, k_ts) && rows16(v, v_bs, v_ts),
-              "attention fwd: K/V rows must be 16-B aligned (strides multiple of 4 floats)");
-  AttnArgs a = attn_base(B, Hh, Tq, Tk, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse,
-                         qpad, kpad, causal, scale);
-  a.qvec = rows16(q, q_bs, q_ts) && (D % 4) == 0;
-  a.ovec = rows16(o, o_bs, o_ts) && (D % 4) == 0;
-  dim3 grid(Hh, B, (Tq + 63) / 64);
-  MRG_ATTN_DISPATCH(attn_fwd_kernel, grid, a);
-  return check_launch("attn_fwd_kernel");
+  return attn_forward(attn_call(B, Hh, Tq, Tk, D, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse,
+                                qpad, kpad, causal, scale, stream, nullptr, nullptr, nullptr));
 }
 
 MRG_API size_t mrg_attention_bwd_workspace_bytes(int B, int Hh, int Tq) {
@@ -873,57 +964,9 @@ MRG_API int mrg_attention_bwd(int B, int Hh, int Tq, int Tk, int D,
                               float* dq, long dq_bs, long dq_ts, float* dk, long dk_bs, long dk_ts,
                               float* dv, long dv_bs, long dv_ts, float* workspace, hipStream_t stream) {
   if (int e = attn_check(D, Tq, Tk, causal)) return e;
-  if (B == 0 || Tq == 0 || Tk == 0) return 0;
-  MRG_REQUIRE(rows16(q, q_bs, q_ts) && rows16(k, k_bs, k_ts) && rows16(v, v_bs, v_ts) &&
-              rows16(dout, do_bs, do_ts), "attention bwd: Q/K/V/dO rows must be 16-B aligned");
-  MRG_REQUIRE(workspace != nullptr, "attention bwd: workspace (B*heads*Tq floats) required");
-  AttnArgs a = attn_base(B, Hh, Tq, Tk, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse,
-                         qpad, kpad, causal, scale);
-  a.dout = dout; a.do_bs = do_bs; a.do_ts = do_ts; a.dlt = workspace;
-  a.dq = dq; a.dq_bs = dq_bs; a.dq_ts = dq_ts; a.dk = dk; a.dk_bs = dk_bs; a.dk_ts = dk_ts;
-  a.dv = dv; a.dv_bs = dv_bs; a.dv_ts = dv_ts;
-  a.qvec = 1;  // required above
-  a.ovec = rows16(o, o_bs, o_ts);
-  a.dkvvec = rows16(dk, dk_bs, dk_ts) && rows16(dv, dv_bs, dv_ts);
-  if (g_attn_fused && D == 64 && Tq <= FTQ && rows16(o, o_bs, o_ts) && a.dkvvec && rows16(dq, dq_bs, dq_ts)) {
-    static bool attr[64] = {};   // the LDS size attribute, set once per device
-    constexpr int bytes = FusedLds<64>::FLOATS * (int)sizeof(float);
-    static_assert(bytes <= 160 * 1024, "fused attention backward: LDS layout exceeds a CU's 160 KB");
-    int dev = 0;
-    MRG_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !attr[dev]) {
-      MRG_HIP(hipFuncSetAttribute((const void*)attn_bwd_fused_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  bytes));
-      if (dev >= 0 && dev < 64) attr[dev] = true;
-    }
-    klaunch(attn_bwd_fused_kernel<64>, dim3(Hh, B), 512, bytes, stream, a);
-    return check_launch("attn_bwd_fused_kernel");
-  }
-  dim3 gq(Hh, B, (Tq + 63) / 64);
-  MRG_ATTN_DISPATCH(attn_bwd_dq_kernel, gq, a);  // also writes delta = rowsum(dO * O) to the workspace
-  if (check_launch("attn_bwd_dq_kernel")) return 1;
-  dim3 gk(Hh, B, (Tk + 63) / 64);
-  MRG_ATTN_DISPATCH(attn_bwd_dkv_kernel, gk, a);
-  return check_launch("attn_bwd_dkv_kernel");
-}
-
-// Attention-probability dropout (nn.MultiheadAttention(dropout = p) in training): the DROP
-// instantiations of the forward and of the two-pass backward.  The single-pass backward and the
-// chunk forms have no dropout variant, so the dispatcher never picks them here.
-#define MRG_ATTN_DISPATCH_DROP(KERNEL, grid, args)                           \
-  switch (D) {                                                               \
-    case 8: klaunch(KERNEL<8, true>, grid, 256, 0, stream, args); break;     \
-    case 16: klaunch(KERNEL<16, true>, grid, 256, 0, stream, args); break;   \
-    case 32: klaunch(KERNEL<32, true>, grid, 256, 0, stream, args); break;   \
-    case 64: klaunch(KERNEL<64, true>, grid, 256, 0, stream, args); break;   \
-  }
-
-static int drop_check(unsigned int thr, float scale_keep, const unsigned long long* key, int B, int Hh) {
-  MRG_REQUIRE(key != nullptr && (((uintptr_t)key) & 7) == 0, "attention dropout: key (2 x uint64, 8-B aligned) required");
-  MRG_REQUIRE(scale_keep >= 1.0f && std::isfinite(scale_keep), "attention dropout: scale_keep = 1 / (1 - p), p in [0, 1)");
-  MRG_REQUIRE((long)B * Hh < 0xFFFFFFFFL, "attention dropout: B * heads too large");
-  (void)thr;
-  return 0;
+  const AttnGrads g = {dout, do_bs, do_ts, dq, dq_bs, dq_ts, dk, dk_bs, dk_ts, dv, dv_bs, dv_ts, workspace};
+  return attn_backward(attn_call(B, Hh, Tq, Tk, D, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse,
+                                 qpad, kpad, causal, scale, stream, &g, nullptr, nullptr));
 }
 
 MRG_API int mrg_attention_fwd_dropout(int B, int Hh, int Tq, int Tk, int D,
@@ -934,17 +977,9 @@ MRG_API int mrg_attention_fwd_dropout(int B, int Hh, int Tq, int Tk, int D,
                                       const unsigned long long* key, hipStream_t stream) {
   if (int e = attn_check(D, Tq, Tk, causal)) return e;
   if (int e = drop_check(thr, scale_keep, key, B, Hh)) return e;
-  if (B == 0 || Tq == 0) return 0;
-  MRG_REQUIRE(rows16(k, k_bs, k_ts) && rows16(v, v_bs, v_ts),
-              "attention fwd: K/V rows must be 16-B aligned (strides multiple of 4 floats)");
-  AttnArgs a = attn_base(B, Hh, Tq, Tk, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse,
-                         qpad, kpad, causal, scale);
-  a.qvec = rows16(q, q_bs, q_ts) && (D % 4) == 0;
-  a.ovec = rows16(o, o_bs, o_ts) && (D % 4) == 0;
-  a.rkey = key; a.thr = thr; a.keep_scale = scale_keep;
-  dim3 grid(Hh, B, (Tq + 63) / 64);
-  MRG_ATTN_DISPATCH_DROP(attn_fwd_kernel, grid, a);
-  return check_launch("attn_fwd_kernel<dropout>");
+  const AttnDrop dr = {thr, scale_keep, key};
+  return attn_forward(attn_call(B, Hh, Tq, Tk, D, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse,
+                                qpad, kpad, causal, scale, stream, nullptr, nullptr, &dr));
 }
 
 MRG_API int mrg_attention_bwd_dropout(int B, int Hh, int Tq, int Tk, int D,
@@ -957,25 +992,10 @@ MRG_API int mrg_attention_bwd_dropout(int B, int Hh, int Tq, int Tk, int D,
                                       float scale_keep, const unsigned long long* key, hipStream_t stream) {
   if (int e = attn_check(D, Tq, Tk, causal)) return e;
   if (int e = drop_check(thr, scale_keep, key, B, Hh)) return e;
-  if (B == 0 || Tq == 0 || Tk == 0) return 0;
-  MRG_REQUIRE(rows16(q, q_bs, q_ts) && rows16(k, k_bs, k_ts) && rows16(v, v_bs, v_ts) &&
-              rows16(dout, do_bs, do_ts), "attention bwd: Q/K/V/dO rows must be 16-B aligned");
-  MRG_REQUIRE(workspace != nullptr, "attention bwd: workspace (B*heads*Tq floats) required");
-  AttnArgs a = attn_base(B, Hh, Tq, Tk, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse,
-                         qpad, kpad, causal, scale);
-  a.dout = dout; a.do_bs = do_bs; a.do_ts = do_ts; a.dlt = workspace;
-  a.dq = dq; a.dq_bs = dq_bs; a.dq_ts = dq_ts; a.dk = dk; a.dk_bs = dk_bs; a.dk_ts = dk_ts;
-  a.dv = dv; a.dv_bs = dv_bs; a.dv_ts = dv_ts;
-  a.qvec = 1;  // required above
-  a.ovec = rows16(o, o_bs, o_ts);
-  a.dkvvec = rows16(dk, dk_bs, dk_ts) && rows16(dv, dv_bs, dv_ts);
-  a.rkey = key; a.thr = thr; a.keep_scale = scale_keep;
-  dim3 gq(Hh, B, (Tq + 63) / 64);
-  MRG_ATTN_DISPATCH_DROP(attn_bwd_dq_kernel, gq, a);  // also writes delta = rowsum(dO * O) to the workspace
-  if (check_launch("attn_bwd_dq_kernel<dropout>")) return 1;
-  dim3 gk(Hh, B, (Tk + 63) / 64);
-  MRG_ATTN_DISPATCH_DROP(attn_bwd_dkv_kernel, gk, a);
-  return check_launch("attn_bwd_dkv_kernel<dropout>");
+  const AttnGrads g = {dout, do_bs, do_ts, dq, dq_bs, dq_ts, dk, dk_bs, dk_ts, dv, dv_bs, dv_ts, workspace};
+  const AttnDrop dr = {thr, scale_keep, key};
+  return attn_backward(attn_call(B, Hh, Tq, Tk, D, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse,
+                                 qpad, kpad, causal, scale, stream, &g, nullptr, &dr));
 }
 
 // Query-chunk forms (the block-level (block, time-chunk) wavefront, block_stack.py): the Tq query
@@ -992,19 +1012,10 @@ MRG_API int mrg_attention_fwd_chunk(int B, int Hh, int Tq, int Tk, int D, int q_
                                     float* lse, const unsigned char* qpad, const unsigned char* kpad,
                                     int causal, float scale, hipStream_t stream) {
   if (int e = attn_check(D, Tq_full, Tk, causal)) return e;
-  MRG_REQUIRE(q_off >= 0 && Tq >= 0 && q_off + Tq <= Tq_full, "attention fwd chunk: rows [%d, %d) outside %d",
-              q_off, q_off + Tq, Tq_full);
-  if (B == 0 || Tq == 0) return 0;
-  MRG_REQUIRE(rows16(k, k_bs, k_ts) && rows16(v, v_bs, v_ts),
-              "attention fwd: K/V rows must be 16-B aligned (strides multiple of 4 floats)");
-  AttnArgs a = attn_base(B, Hh, Tq, Tk, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse,
-                         qpad ? qpad + q_off : nullptr, kpad, causal, scale);
-  a.q_off = q_off; a.Tqf = Tq_full; a.qp_bs = Tq_full; a.st_ld = Tq_full; a.st_off = q_off;
-  a.qvec = rows16(q, q_bs, q_ts) && (D % 4) == 0;
-  a.ovec = rows16(o, o_bs, o_ts) && (D % 4) == 0;
-  dim3 grid(Hh, B, (Tq + 63) / 64);
-  MRG_ATTN_DISPATCH(attn_fwd_kernel, grid, a);
-  return check_launch("attn_fwd_kernel");
+  if (int e = chunk_check("fwd", q_off, Tq, Tq_full)) return e;
+  const AttnChunk ch = {q_off, Tq_full, 0, 0};
+  return attn_forward(attn_call(B, Hh, Tq, Tk, D, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse,
+                                qpad, kpad, causal, scale, stream, nullptr, &ch, nullptr));
 }
 
 MRG_API int mrg_attention_bwd_chunk(int B, int Hh, int Tq, int Tk, int D, int q_off, int Tq_full,
@@ -1016,37 +1027,10 @@ MRG_API int mrg_attention_bwd_chunk(int B, int Hh, int Tq, int Tk, int D, int q_
                                     float* dv, long dv_bs, long dv_ts, int passes, int kv_accumulate,
                                     float* workspace, hipStream_t stream) {
   if (int e = attn_check(D, Tq_full, Tk, causal)) return e;
-  MRG_REQUIRE(q_off >= 0 && Tq >= 0 && q_off + Tq <= Tq_full, "attention bwd chunk: rows [%d, %d) outside %d",
-              q_off, q_off + Tq, Tq_full);
-  if (B == 0 || Tq == 0 || Tk == 0) return 0;
-  MRG_REQUIRE(rows16(q, q_bs, q_ts) && rows16(k, k_bs, k_ts) && rows16(v, v_bs, v_ts) &&
-              rows16(dout, do_bs, do_ts), "attention bwd: Q/K/V/dO rows must be 16-B aligned");
-  MRG_REQUIRE(workspace != nullptr, "attention bwd: workspace (B*heads*Tq_full floats) required");
-  MRG_REQUIRE(passes >= 1 && passes <= 3, "attention bwd chunk: passes %d (1 dQ, 2 dK/dV, 3 both)", passes);
-  AttnArgs a = attn_base(B, Hh, Tq, Tk, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse,
-                         qpad ? qpad + q_off : nullptr, kpad, causal, scale);
-  a.q_off = q_off; a.Tqf = Tq_full; a.qp_bs = Tq_full; a.kv_acc = kv_accumulate ? 1 : 0;
-  a.st_ld = Tq_full; a.st_off = q_off;
-  a.dout = dout; a.do_bs = do_bs; a.do_ts = do_ts; a.dlt = workspace;
-  a.dq = dq; a.dq_bs = dq_bs; a.dq_ts = dq_ts; a.dk = dk; a.dk_bs = dk_bs; a.dk_ts = dk_ts;
-  a.dv = dv; a.dv_bs = dv_bs; a.dv_ts = dv_ts;
-  a.qvec = 1;
-  a.ovec = rows16(o, o_bs, o_ts);
-  a.dkvvec = rows16(dk, dk_bs, dk_ts) && rows16(dv, dv_bs, dv_ts);
-  if (passes & 1) {   // dQ and delta (the dK / dV pass reads delta from the workspace)
-    dim3 gq(Hh, B, (Tq + 63) / 64);
-    MRG_ATTN_DISPATCH(attn_bwd_dq_kernel, gq, a);
-    if (check_launch("attn_bwd_dq_kernel")) return 1;
-  }
-  if (!(passes & 2)) return 0;
-  // accumulating: only the key blocks the chunk's last query can see (the rest get nothing)
-  int tk = Tk;
-  if (a.kv_acc && causal) {
-    const int gl = q_off + Tq - 1;
-    tk = (Tk >= Tq_full) ? (gl + 1) * (Tk / Tq_full) : gl / (Tq_full / Tk) + 1;
-    tk = tk < Tk ? tk : Tk;
-  }
-  dim3 gk(Hh, B, (tk + 63) / 64);
-  MRG_ATTN_DISPATCH(attn_bwd_dkv_kernel, gk, a);
-  return check_launch("attn_bwd_dkv_kernel");
+  if (int e = chunk_check("bwd", q_off, Tq, Tq_full)) return e;
+  const AttnGrads g = {dout, do_bs, do_ts, dq, dq_bs, dq_ts, dk, dk_bs, dk_ts, dv, dv_bs, dv_ts, workspace};
+  const AttnChunk ch = {q_off, Tq_full, passes, kv_accumulate};
+  return attn_backward(attn_call(B, Hh, Tq, Tk, D, q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, o, o_bs, o_ts, lse,
+                                 qpad, kpad, causal, scale, stream, &g, &ch, nullptr));
 }
+

@@ -29,6 +29,7 @@
 // that adds the blocks' partials in block order: no atomics, the same bits on every run.
 #include "mrg_common.h"
 #include "rng.h"
+#include "attention_tiles.h"   // rows16
 
 namespace mrg {
 
@@ -255,10 +256,6 @@ __global__ __launch_bounds__(256) void attn_extra_reduce_kernel(const float* par
 
 using namespace mrg;
 
-static bool x16(const void* p, long bs, long ts) {
-  return p == nullptr || ((((uintptr_t)p) & 15) == 0 && (bs & 3) == 0 && (ts & 3) == 0);
-}
-
 static int extra_check(int B, int Hh, int Tq, int Tk, int D, float keep_scale, const unsigned long long* rkey) {
   MRG_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64, "attention extra keys: unsupported head dim %d", D);
   MRG_REQUIRE(B >= 0 && Tq >= 0 && Tk >= 0 && Hh >= 1 && (long)Hh * D <= XE_MAX,
@@ -292,7 +289,7 @@ MRG_API int mrg_attention_extra_fwd(int B, int Hh, int Tq, int D, const float* q
   a.o = o; a.o_bs = o_bs; a.o_ts = o_ts; a.lse = lse;
   a.B = B; a.Hh = Hh; a.Tq = Tq; a.Tk = Tk; a.D = D; a.E = Hh * D; a.zero = zero_attn ? 1 : 0; a.scale = scale;
   a.rkey = bias_k ? rkey : nullptr; a.thr = thr; a.keep_scale = keep_scale;   // the zero key's value is 0: kept or not
-  const bool vec = x16(q, q_bs, q_ts) && x16(o, o_bs, o_ts) && x16(bias_k, 0, 0) && x16(bias_v, 0, 0);
+  const bool vec = rows16(q, q_bs, q_ts) && rows16(o, o_bs, o_ts) && rows16(bias_k, 0, 0) && rows16(bias_v, 0, 0);
   const dim3 grid((unsigned)(((long)B * Tq + 3) / 4));
   if (vec) klaunch(attn_extra_fwd_kernel<4>, grid, 256, 0, stream, a);
   else klaunch(attn_extra_fwd_kernel<1>, grid, 256, 0, stream, a);
@@ -337,8 +334,8 @@ MRG_API int mrg_attention_extra_bwd(int B, int Hh, int Tq, int D, const float* q
   a.pk = pk; a.pk_bs = pk_bs; a.pk_ts = pk_ts; a.lse_main = lse_main; a.cbuf = cbuf; a.part = workspace;
   a.B = B; a.Hh = Hh; a.Tq = Tq; a.Tk = Tk; a.D = D; a.E = E; a.scale = scale;
   a.rkey = rkey; a.thr = thr; a.keep_scale = keep_scale;
-  const bool vec = x16(q, q_bs, q_ts) && x16(o, o_bs, o_ts) && x16(dout, do_bs, do_ts) && x16(dq, dq_bs, dq_ts) &&
-                   x16(pk, pk_bs, pk_ts) && x16(bias_k, 0, 0) && x16(bias_v, 0, 0);
+  const bool vec = rows16(q, q_bs, q_ts) && rows16(o, o_bs, o_ts) && rows16(dout, do_bs, do_ts) && rows16(dq, dq_bs, dq_ts) &&
+                   rows16(pk, pk_bs, pk_ts) && rows16(bias_k, 0, 0) && rows16(bias_v, 0, 0);
   const int nblk = extra_blocks((long)B * Tq);
   const unsigned lds = 4u * 2u * (unsigned)E * sizeof(float);   // at most 32 KB
   if (vec) klaunch(attn_extra_bwd_kernel<4>, dim3(nblk), 256, lds, stream, a);

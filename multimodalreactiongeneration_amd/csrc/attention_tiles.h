@@ -42,6 +42,12 @@ struct AttnArgs {
   float keep_scale;
 };
 
+// host: the rows of a [B, T, ...] operand (pointer, batch and row stride in floats) are 16-B aligned, so
+// float4 loads and stores apply; an operand that is not there passes
+inline bool rows16(const void* p, long bs, long ts) {
+  return p == nullptr || ((((uintptr_t)p) & 15) == 0 && (bs & 3) == 0 && (ts & 3) == 0);
+}
+
 __device__ __forceinline__ long stat_row(const AttnArgs& a, int b, int h, int qi) {
   return ((long)b * a.Hh + h) * a.st_ld + a.st_off + qi;
 }

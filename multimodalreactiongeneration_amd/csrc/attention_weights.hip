@@ -179,10 +179,6 @@ __global__ __launch_bounds__(256) void attn_weights_kernel(WeightArgs w) {
 
 using namespace mrg;
 
-static bool rows16(const float* p, long bs, long ts) {
-  return p == nullptr || ((((uintptr_t)p) & 15) == 0 && (bs & 3) == 0 && (ts & 3) == 0);
-}
-
 #define MRG_WEIGHTS_DISPATCH(AVG)                                                         \
   switch (D) {                                                                            \
     case 8: klaunch(attn_weights_kernel<8, AVG>, grid, 256, 0, stream, w); break;         \

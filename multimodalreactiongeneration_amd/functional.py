@@ -17,18 +17,18 @@ Reference ops replaced (file:line in /root/reference):
   masked_loss         training_step / lossfun     lstmformer.py:313-325,372-380
 
 This module only re-exports.  The code lives, in import order, in launch (plumbing), gemm_ops (GEMM
-dispatch), then dense, recurrent, attention and losses; a switch that is rebound, not mutated
+dispatch), then dense, recurrent, dropout, attention and losses; a switch that is rebound, not mutated
 (dense.RELU_TAP, gemm_ops.wgrad_splits), must be set on the module that owns it.
 """
-from .attention import (_DropoutFn, _MHAFn, _MHAOneKeyFn, _RNG, _drop_consts, _i64, _one_key,  # noqa: F401
-                        _rng_device, _rng_draw, _rng_state, attention_keep_mask, dropout, dropout_keep_mask,
-                        get_rng_state, manual_seed, mha, mha_residual, mha_residual_layernorm, set_rng_state,
-                        visible_pairs)
+from .attention import (MHASpec, _MHAFn, _MHAOneKeyFn, _one_key, attn_bwd, attn_fwd, mha, mha_residual,  # noqa: F401
+                        mha_residual_layernorm, visible_pairs)
 from .dense import (ACTIVATIONS, RELU_TAP, _ActFn, _FFNFn, _FFNResFn, _FFNResLNFn, _LinAddFn, _LinearFn,  # noqa: F401
                     _LinResFn, _LinResLNFn, _MLPChainFn, _ResAddFn, _ResLNFn, _Sample0Fn, _act_codes,
                     _act_fwd_gemm, _resln_bwd, _resln_fwd, _tap_relu, activation, broadcast_sample0, ffn,
                     ffn_residual, ffn_residual_layernorm, linear, linear_add, linear_residual,
                     linear_residual_layernorm, mlp_chain, residual_add, residual_layernorm)
+from .dropout import (_DropoutFn, _RNG, _drop_consts, _i64, _rng_device, _rng_draw, _rng_state,  # noqa: F401
+                      attention_keep_mask, dropout, dropout_keep_mask, get_rng_state, manual_seed, set_rng_state)
 from .gemm_ops import (_CNT, _PL_ON, _PLANES, _WG_TARGET, _WT_CACHE, _WT_MIN_ROWS, _WT_ON, _WT_PENDING,  # noqa: F401
                        _counters, _dx_gemm, _fwd_gemm, _on_side, _plane_operand, _planes_gemm, _wgrad, _wt,
                        _wt_key, _wt_note, act_splits, colsum, gemm, invalidate_weight_planes, planes_batched,

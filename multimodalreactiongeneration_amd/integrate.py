@@ -31,7 +31,7 @@ from torch.autograd import Function
 
 from . import _lib
 from . import gemm_ops
-from .attention import visible_pairs
+from .attention import attn_bwd, attn_fwd
 from .gemm_ops import _dx_gemm, _wt_note, gemm
 from .launch import _ARITH, _gbuf, _keeps_precision, _probe, _ptr, _stream, _ws
 from .model.forms import Integrator
@@ -130,7 +130,6 @@ class _IntegrateFn(Function):
         cat_w, cat_b = t[1 + 3 * n + _PER * n:]
         _lib.require_device(q_in)
         dev = q_in.device
-        lib = _lib.load()
         B, Tq, E = q_in.shape
         D = E // heads
         N = B * Tq
@@ -154,12 +153,8 @@ class _IntegrateFn(Function):
         lse = torch.empty(n, B, heads, Tq, **f32)
         scale = 1.0 / math.sqrt(D)
         for i in range(n):
-            Tk = kv2[i].shape[1]
-            with _probe("attn_fwd", 4.0 * D * B * heads * visible_pairs(Tq, Tk, causal)):
-                rc = lib.mrg_attention_fwd(B, heads, Tq, Tk, D, _ptr(Q[i]), Tq * E, E, _ptr(KV[i]), Tk * 2 * E,
-                                           2 * E, _p(KV[i], E), Tk * 2 * E, 2 * E, _ptr(O[i]), Tq * E, E,
-                                           _ptr(lse[i]), _ptr(qpads[i]), _ptr(kpads[i]), int(causal), scale, _stream())
-            _lib.check(rc, "attention fwd (integrator)")
+            attn_fwd(heads, Q[i], KV[i], O[i], lse[i], qpads[i], kpads[i], causal, scale, probe=True,
+                     what="attention fwd (integrator)")
         A = torch.empty(n, N, E, **f32)    # attention outputs after out_proj
         _bgemm(N, E, E, [(_ptr(O[i]), P[i].out_w, _ptr(A[i]), _ptr(P[i].out_b), None) for i in range(n)], E, E, dev=dev)
         U = torch.empty(n, N, E, **f32)
@@ -196,7 +191,6 @@ class _IntegrateFn(Function):
         KV, kpads = list(s[12 + 2 * n:12 + 3 * n]), list(s[12 + 3 * n:12 + 4 * n])
         P, cat_w, cat_b = ctx.params
         B, Tq, E = q2.shape
-        D = E // heads
         N = B * Tq
         dev = dout.device
         lib = _lib.load()
@@ -221,15 +215,9 @@ class _IntegrateFn(Function):
         dQ = torch.empty(n, N, E, **f32)
         dKV = [torch.empty(B, kv.shape[1], 2 * E, **f32) for kv in kv2]
         for i in range(n):
-            Tk = kv2[i].shape[1]
             ws = _ws(lib.mrg_attention_bwd_workspace_bytes(B, heads, Tq), dev)
-            with _probe("attn_bwd", 10.0 * D * B * heads * visible_pairs(Tq, Tk, causal)):
-                rc = lib.mrg_attention_bwd(
-                    B, heads, Tq, Tk, D, _ptr(Q[i]), Tq * E, E, _ptr(KV[i]), Tk * 2 * E, 2 * E, _p(KV[i], E),
-                    Tk * 2 * E, 2 * E, _ptr(O[i]), Tq * E, E, _ptr(lse[i]), _ptr(qpads[i]), _ptr(kpads[i]), int(causal),
-                    scale, _ptr(dO[i]), Tq * E, E, _ptr(dQ[i]), Tq * E, E, _ptr(dKV[i]), Tk * 2 * E, 2 * E,
-                    _p(dKV[i], E), Tk * 2 * E, 2 * E, _ptr(ws), _stream())
-            _lib.check(rc, "attention bwd (integrator)")
+            attn_bwd(heads, Q[i], KV[i], O[i], lse[i], qpads[i], kpads[i], causal, scale, dO[i], dQ[i], dKV[i], ws,
+                     probe=True, what="attention bwd (integrator)")
         dq = None
         if ctx.q_need:   # dq = sum_i (dQ_i W_q_i + g1_i): two epilogue-3 GEMMs into one buffer
             dq = torch.empty(B, Tq, E, **f32)

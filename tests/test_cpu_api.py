@@ -266,7 +266,7 @@ def test_side_stream_flush_conflicts():
 
 # ------------------------------------------------------------------ functional.py is a facade over layered modules
 PKG = "multimodalreactiongeneration_amd"
-LAYERS = (("launch",), ("gemm_ops",), ("dense", "recurrent", "attention", "losses"))   # import order, top first
+LAYERS = (("launch",), ("gemm_ops",), ("dense", "recurrent", "dropout", "attention", "losses"))   # import order, top first
 ALIASES = {"_side": "side"}   # functional's name -> the owner's name, where they differ
 
 
@@ -312,7 +312,7 @@ def test_functional_modules_import_only_upward():
     attention from dense, for the residual LayerNorm), from _lib, rng and wgrad_streams, never from
     functional; wgrad_streams and _lib import none of them."""
     allowed = {"_lib", "wgrad_streams", "rng"}
-    same_layer = {"recurrent": {"dense"}, "attention": {"dense"}}
+    same_layer = {"recurrent": {"dense"}, "attention": {"dense", "dropout"}}
     for layer in LAYERS:
         for mod in layer:
             got = _package_imports(mod)

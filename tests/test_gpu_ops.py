@@ -867,9 +867,9 @@ def test_mha_one_key_shortcut_matches_attention_kernel(resln, masked):
         extra = (ps[4], ps[5]) if resln else ()
         eps = 1e-5 if resln else None
         if one_key:
-            y = Fn._MHAOneKeyFn.apply(eps, qq, kk, *ps[:4], qpad, kpad, *extra)
+            y = Fn._MHAOneKeyFn.apply(Fn.MHASpec(heads, True, eps), qq, kk, *ps[:4], qpad, kpad, *extra)
         else:
-            y = Fn._MHAFn.apply((heads, True, eps), qq, kk, *ps[:4], qpad, kpad, *extra)
+            y = Fn._MHAFn.apply(Fn.MHASpec(heads, True, eps), qq, kk, *ps[:4], qpad, kpad, *extra)
         (y[keep] * dy.to(DEV)[keep]).sum().backward()
         torch.cuda.synchronize()
         outs.append((y.detach(), qq.grad, kk.grad, [None if p.grad is None else p.grad.clone() for p in ps]))
